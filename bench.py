@@ -10,6 +10,12 @@ N GPUs = tensor parallelism over N ranks (one process per GPU, RCCL), the SSM
 replicated per rank.  value = decoded tokens of all requests / wall time
 (max over ranks).
 
+A plain run sets up, warms up, times --steps generates and prints the result
+line; --dump-outputs DIR also writes the last timed generate's tokens.  --full
+adds everything beside the headline after the timed steps: the sampled op
+breakdown / roofline, the incremental-decoding side run, the side legs and
+the CPU baseline.
+
 The process never imports torch (torch bundles a second copy of the HIP
 runtime); the multi-rank control plane (unique-id broadcast, barrier,
 max-reduce of times) is a small TCP exchange on 127.0.0.1.
@@ -173,6 +179,21 @@ def run_generate(rm, llm, prompts, max_length, spec):
     new = sum(len(r.output_tokens) - len(r.input_tokens) for r in res)
     lat = [(r.latency_us / max(1, len(r.output_tokens) - len(r.input_tokens))) for r in res]
     return new, lat, res
+
+
+def dump_outputs(folder, res):
+    """What the last timed generate() returned, as .npy files: every request's
+    token ids (BOS + prompt + decoded tokens) in one float64 array, rows
+    padded with -1, and the rows' lengths.  Prompts and weights are seeded,
+    so the same arguments give the same arrays from run to run."""
+    import numpy as np
+    os.makedirs(folder, exist_ok=True)
+    lens = [len(r.output_tokens) for r in res]
+    toks = np.full((len(res), max(lens)), -1.0, np.float64)
+    for i, r in enumerate(res):
+        toks[i, :lens[i]] = r.output_tokens
+    np.save(os.path.join(folder, "output_tokens.npy"), toks)
+    np.save(os.path.join(folder, "output_lengths.npy"), np.array(lens, np.float64))
 
 
 def cpu_baseline(acceptance=1.0, prompt_len=128, batch=8, budget_s=12.0, incr_budget_s=8.0):
@@ -360,13 +381,27 @@ def main():
     ap.add_argument("--prefill", type=int, default=128)
     ap.add_argument("--decode", type=int, default=128)
     ap.add_argument("--max-tokens-per-batch", type=int, default=1024)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-incr", action="store_true", help="skip the incr-decoding side run")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything beside the headline: the "
+                         "sampled op breakdown / roofline, the incr-decoding side run, the "
+                         "side legs and the CPU baseline (each has its own --no-* switch); "
+                         "without it a run sets up, warms up, times --steps generates and "
+                         "prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed generate returned to DIR/output_tokens.npy "
+                         "(float64 [requests][tokens], rows padded with -1) and "
+                         "DIR/output_lengths.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-incr", action="store_true",
+                    help="with --full: skip the incr-decoding side run")
     ap.add_argument("--no-legs", action="store_true",
-                    help="skip the side legs (tree width 4, 4 SSMs, token-chain acceptance)")
+                    help="with --full: skip the side legs (tree width 4, 4 SSMs, token-chain "
+                         "acceptance)")
     ap.add_argument("--profile", type=int, default=1,
-                    help="op profiling level of the sampled generates run AFTER the timed "
-                         "ones (roofline, op breakdown); the timed region never profiles")
+                    help="with --full: op profiling level of the sampled generates run AFTER "
+                         "the timed ones (roofline, op breakdown); the timed region never "
+                         "profiles")
     ap.add_argument("--profile-generates", type=int, default=2,
                     help="untimed generates sampled for the op breakdown")
     ap.add_argument("--layers", type=int, default=0, help="override LLM layer count (debug)")
@@ -379,6 +414,8 @@ def main():
                     help="launcher + control plane only, no GPU (CPU test of the N-rank path)")
     ap.add_argument("--dry-run-fail-rank", type=int, default=-1, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         sys.exit(launch_ranks(sys.argv[1:], args.gpus))
@@ -528,11 +565,13 @@ def main():
     device_sync()
     ctrl.barrier()
     elapsed = ctrl.max(time.time() - t0)
-    # op breakdown / roofline: sampled in extra generates after the timed
-    # region (op profiling runs every 4th step eager with events around the
-    # ops of layers 0 and L/2), so the timed steps run as in production
+    if args.dump_outputs and rank == 0:  # (every rank decodes the same tokens)
+        dump_outputs(args.dump_outputs, res)
+    # op breakdown / roofline (--full): sampled in extra generates after the
+    # timed region (op profiling runs every 4th step eager with events around
+    # the ops of layers 0 and L/2), so the timed steps run as in production
     ops = {}
-    if args.profile and args.profile_generates > 0:
+    if args.full and args.profile and args.profile_generates > 0:
         llm.set_profiling(args.profile)
         for _ in range(args.profile_generates):
             run_generate(rm, llm, prompts, max_len, spec)
@@ -618,7 +657,8 @@ def main():
             kk: {"avg_us": round(1000 * v["ms"] / v["launches"], 2),
                  "GBps": round(v["bytes"] / (v["ms"] * 1e-3) / 1e9, 1) if v["ms"] else None,
                  "launches": v["launches"]} for kk, v in ops.items()}
-    if rank == 0 and world == 1 and spec and not args.no_incr:
+    side = args.full and rank == 0 and world == 1  # the side runs: one GPU, --full only
+    if side and spec and not args.no_incr:
         inc = fa.Model(llm_cfg, "inc", max_requests=B, max_tokens=mtb,
                        max_seq_len=rm_kw["max_sequence_length"], weight_seed=20250117,
                        weights_folder=args.llm_weights)
@@ -631,7 +671,7 @@ def main():
                                 "p50_token_latency_ms": round(statistics.median(lat) / 1000, 3),
                                 "llm_steps": rmi.stats().llm_steps}
         inc.close()
-    if rank == 0 and world == 1 and spec and not args.no_legs:
+    if side and spec and not args.no_legs:
         # side legs, one warm + one timed generate each, same prompts and
         # lengths as the headline (BASELINE configs C / E as stated, and
         # SpecInfer at the acceptance a trained SSM gives):
@@ -653,7 +693,7 @@ def main():
         for name, lg in legs.items():
             out[name] = run_leg(llm_cfg, ssm_cfg, prompts, max_len, B, mtb, rm_kw, args, **lg)
             progress(f"leg {name}: {out[name]['value']} tokens/s")
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if side and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(
             acceptance=out.get("tokens_per_request_verify", 1.0) if spec else 1.0)
     if rank == 0:

@@ -578,7 +578,9 @@ __global__ __launch_bounds__(64 * NW, 1) void attention_kernel(
 #pragma unroll
           for (int i = 0; i < TK; ++i) {
             const int e = threadIdx.x + i * NT, row = e / D8;
-            if (row < told) *reinterpret_cast<uint4 *>(&sKt[row][(e % D8) * 8]) = tk[i];
+            if (row < told)  // (by field: copied whole, tk[] went to scratch at TK == 2)
+              *reinterpret_cast<uint4 *>(&sKt[row][(e % D8) * 8]) =
+                  make_uint4(tk[i].x, tk[i].y, tk[i].z, tk[i].w);
           }
 #pragma unroll
           for (int i = 0; i < TV; ++i) {

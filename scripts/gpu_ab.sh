@@ -11,8 +11,8 @@
 set -o pipefail
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd "$R"; mkdir -p gpurun_out
-REPS=1; BARGS="--no-cpu-baseline --no-incr --steps 3 --warmup 1"
-while getopts "r:b:" o; do case $o in r) REPS=$OPTARG;; b) BARGS="--no-cpu-baseline --steps 3 --warmup 1 $OPTARG";; *) exit 2;; esac; done
+REPS=1; BARGS="--full --no-cpu-baseline --no-incr --steps 3 --warmup 1"
+while getopts "r:b:" o; do case $o in r) REPS=$OPTARG;; b) BARGS="--full --no-cpu-baseline --steps 3 --warmup 1 $OPTARG";; *) exit 2;; esac; done
 shift $((OPTIND - 1))
 : > gpurun_out/ab.log
 for rep in $(seq "$REPS"); do

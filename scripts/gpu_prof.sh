@@ -8,7 +8,7 @@ set -o pipefail
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd "$R"; mkdir -p gpurun_out
 TAG=$1; shift
-BARGS="--steps 1 --warmup 1 --no-cpu-baseline --no-incr --profile 0"
+BARGS="--full --steps 1 --warmup 1 --no-cpu-baseline --no-incr --profile 0"
 if [ "$1" = "-b" ]; then BARGS="$BARGS $2"; shift 2; fi
 [ $# -eq 0 ] && set -- ""
 export TMPDIR=/tmp DEBUG_CLR_GRAPH_PACKET_CAPTURE=0

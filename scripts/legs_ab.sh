@@ -11,7 +11,7 @@ shift $((OPTIND - 1))
 : > gpurun_out/legs_ab.log
 for rep in $(seq "$REPS"); do
   for ARM in "$@"; do
-    env $ARM timeout -k 10 400 python bench.py --no-cpu-baseline --no-incr --steps 2 --warmup 1 \
+    env $ARM timeout -k 10 400 python bench.py --full --no-cpu-baseline --no-incr --steps 2 --warmup 1 \
       > gpurun_out/legs_run.json 2> gpurun_out/legs_run.err || {
       echo "arm '$ARM' failed"; tail -5 gpurun_out/legs_run.err; exit 1; }
     python3 - "$ARM" "$rep" <<'PY' | tee -a gpurun_out/legs_ab.log

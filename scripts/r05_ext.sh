@@ -19,7 +19,7 @@ tests)
   $S ext_65b 1000 $PT --timeout 980 tests/test_gpu_llama65b_tp.py -k "ssm4" || exit 1
   ;;
 bench)
-  $S ext_bench 600 python -u bench.py --steps 3 --warmup 1 --no-cpu-baseline || exit 1
+  $S ext_bench 600 python -u bench.py --full --steps 3 --warmup 1 --no-cpu-baseline || exit 1
   ;;
 neg)
   $S ext_neg 600 $PT --timeout 580 tests/test_gpu_bench_workload.py -k "negative" || exit 1

@@ -13,6 +13,6 @@ run ${TAG}_topk 120 python scripts/topk_bench.py && \
  timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d /tmp/${TAG}_tl -o bench -- python3 "$R/bench.py" --steps 1 --warmup 1 --no-cpu-baseline --no-incr --no-legs --profile 0 > "$R/gpurun_out/${TAG}_tl.log" 2>&1) && \
 cp /tmp/${TAG}_tl/bench_kernel_trace.csv gpurun_out/${TAG}_trace.csv && \
 python3 scripts/step_timeline.py gpurun_out/${TAG}_trace.csv --gap 6 --skip 40 > gpurun_out/${TAG}_timeline.txt && \
-run ${TAG}_bench_p0 300 python bench.py --no-cpu-baseline --no-legs --steps 5 --warmup 2 --profile 0 && \
-run ${TAG}_bench_p1 300 python bench.py --no-cpu-baseline --no-legs --steps 5 --warmup 2 --profile 1 && \
+run ${TAG}_bench_p0 300 python bench.py --full --no-cpu-baseline --no-legs --steps 5 --warmup 2 --profile 0 && \
+run ${TAG}_bench_p1 300 python bench.py --full --no-cpu-baseline --no-legs --steps 5 --warmup 2 --profile 1 && \
 run ${TAG}_bench_p0b 300 python bench.py --no-cpu-baseline --no-legs --no-incr --steps 5 --warmup 2 --profile 0

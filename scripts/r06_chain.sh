@@ -9,7 +9,7 @@ run() { local n=$1 t=$2; shift 2; timeout -k 10 "$t" "$@" > "gpurun_out/$n.log" 
 run ${TAG}_tests 600 python -u -m pytest -x -q --timeout 120 --timeout-method thread -m gpu tests/test_gpu_e2e.py tests/test_gpu_kernels.py -k "e2e or softmax or topk or argmax or chained or spec or graph" && \
 run ${TAG}_bench1 300 python bench.py --no-cpu-baseline --no-legs --no-incr --steps 5 --warmup 2 --profile 0 && \
 FFMI_SSM_CHAIN=0 run ${TAG}_bench0 300 python bench.py --no-cpu-baseline --no-legs --no-incr --steps 5 --warmup 2 --profile 0 && \
-run ${TAG}_bench1b 300 python bench.py --no-cpu-baseline --no-incr --steps 5 --warmup 2 --profile 0 && \
+run ${TAG}_bench1b 300 python bench.py --full --no-cpu-baseline --no-incr --steps 5 --warmup 2 --profile 0 && \
 for f in bench1 bench0 bench1b; do python3 - "gpurun_out/${TAG}_$f.log" <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])

@@ -36,6 +36,19 @@ def test_dead_rank_fails_fast():
     assert time.time() - t0 < 60  # rank 0 is killed, not left waiting on accept()
 
 
+def test_full_and_dump_outputs_are_options(tmp_path):
+    # (a dry run computes nothing, so it writes nothing either)
+    p = run("--gpus", "1", "--dry-run", "--full", "--dump-outputs", str(tmp_path / "out"))
+    assert p.returncode == 0, p.stderr
+    assert json.loads(p.stdout)["metric"] == "dry-run"
+    assert not (tmp_path / "out").exists()
+
+
+def test_zero_timed_steps_rejected():
+    p = run("--gpus", "1", "--dry-run", "--steps", "0")
+    assert p.returncode != 0 and "--steps" in p.stderr
+
+
 def test_world_size_mismatch_rejected():
     env = dict(os.environ, RANK="0", WORLD_SIZE="2")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4",
