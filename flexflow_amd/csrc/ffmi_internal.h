@@ -126,6 +126,31 @@ __device__ __forceinline__ float partials_value(const float *p, int S, int NP, i
   return __half2float(__float2half_rn(acc));
 }
 
+// Placement of a split-K M-split launch, grid (nblk, S, mblocks): which
+// (tile block cb, k-slice ks) the workgroup at blockIdx (bx, by) computes.
+// Workgroups are dealt to the 8 XCDs round-robin in linear order (x fastest),
+// so with the identity numbering every XCD holds column blocks of ALL S slices
+// and its L2 pulls in the whole activation matrix.  The map gives the
+// workgroups of one residue (linear id % 8) a CONTIGUOUS run of
+// L = ks * nblk + cb: a slice's column blocks share as few XCDs as possible
+// (nblk * S a multiple of 8 and S | 8: each slice exactly 8 / S of them,
+// each XCD one slice) and an XCD fetches only its slices' X columns.  The
+// linear id within a z plane is split as gemm_tile_kernel's: residue x gets
+// q + 1 ids when x < r, q otherwise (q, r = nblk * S / 8, nblk * S % 8), so
+// the map is a bijection of the plane for every (nblk, S); z is untouched
+// and every plane uses the same map, so row blocks of a weight tile share a
+// residue exactly where they did.  Speed only: nothing depends on where a
+// workgroup really runs.  S == 1 is the identity.
+__host__ __device__ __forceinline__ void mid_xcd_map(int bx, int by, int nblk, int S, int &cb,
+                                                     int &ks) {
+  cb = bx, ks = by;
+  if (S <= 1) return;
+  const int l = bx + nblk * by, P = nblk * S;
+  const int x = l & 7, q = P >> 3, r = P & 7;
+  const int L = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (l >> 3);
+  ks = L / nblk, cb = L - ks * nblk;
+}
+
 // ---- kernel launchers (defined in kernels/*.hip) ----
 hipError_t launch_fill_weight(uint16_t *dst, size_t n, uint64_t key, int kind, hipStream_t s,
                               int cols = 0, uint64_t pa = 1, uint64_t pb = 0, float scale = 1.0f);

@@ -787,7 +787,7 @@ template <int MTW, int NTW, int PF, int EPI, bool STAMP = false, bool XP = false
 __global__ __launch_bounds__(256, NTW <= 8 && MTW * NTW <= 24 ? 2 : 1) void gemm_mid_kernel(
     const uint16_t *__restrict__ X, const uint16_t *__restrict__ Wp,
     uint16_t *__restrict__ Y, float *__restrict__ Ypart, int T, int N, int K, int KT,
-    int NTILES, int S, int yp, size_t wts, size_t wks) {
+    int NTILES, int S, int yp, size_t wts, size_t wks, int xmap) {
   long long st0 = 0, st1 = 0, st2 = 0, ck1 = 0, ck2 = 0;
   if (STAMP) st0 = rt_now();
   static_assert(NTW % 2 == 0, "gate/up tiles come in pairs");
@@ -798,8 +798,11 @@ __global__ __launch_bounds__(256, NTW <= 8 && MTW * NTW <= 24 ? 2 : 1) void gemm
   __shared__ __attribute__((aligned(16))) h8 sB[2][NTW][64];
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
-  const int tile0 = blockIdx.x * NTW;
-  const int ks = blockIdx.y;
+  // (tile block, k-slice) of this workgroup: blockIdx, or renumbered so that
+  // the workgroups of a slice share XCDs (mid_xcd_map, ffmi_internal.h)
+  int cb = blockIdx.x, ks = blockIdx.y;
+  if (xmap) mid_xcd_map(blockIdx.x, blockIdx.y, gridDim.x, S, cb, ks);
+  const int tile0 = cb * NTW;
   const int m0 = blockIdx.z * (4 * MTW * 16) + wave * MTW * 16;
   const int per = (KT + S - 1) / S;
   const int kb = min(KT, ks * per);
@@ -905,7 +908,8 @@ __global__ __launch_bounds__(256, NTW <= 8 && MTW * NTW <= 24 ? 2 : 1) void gemm
     asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
     asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
     if (lane == 0 && g_gemm_stamps) {
-      const long b = blockIdx.x + (long)gridDim.x * (blockIdx.y + (long)gridDim.y * blockIdx.z);
+      // (indexed by what the workgroup computed; d[5] tells where it ran)
+      const long b = cb + (long)gridDim.x * (ks + (long)gridDim.y * blockIdx.z);
       long long *d = g_gemm_stamps + (b * 4 + wave) * 8;
       d[0] = st0; d[1] = st1; d[2] = st2; d[3] = st3; d[4] = hwid; d[5] = xcc;
       d[6] = ck1; d[7] = ck2;
@@ -1187,6 +1191,15 @@ static hipError_t run_mid(const uint16_t *X, const uint16_t *Wp, uint16_t *Y, fl
   const size_t need = (size_t)S * T * ntiles * 16 * sizeof(float);
   if (S > 1 && (!ws || ws_bytes < need)) S = 1;  // no workspace: un-split (slower)
   dim3 grid(nblk, S, mblocks);
+  // split-K launches: the workgroups of a k-slice renumbered onto the same
+  // XCDs, so that an XCD's L2 fetches only its slices' X columns
+  // (mid_xcd_map).  From 4 slices on: with 2 (qkv at T = 168) every XCD still
+  // needs half of X and the launch measured no faster.
+  // FFMI_MID_XCD: 0 blockIdx numbering, 1 the default, 2 every split launch
+  // (A/B runs and tests; read per call)
+  const char *xe = getenv("FFMI_MID_XCD");
+  const int xmode = xe ? atoi(xe) : 1;
+  const int xmap = xmode != 0 && S >= (xmode == 2 ? 2 : 4);
   static const bool stamp = getenv("FFMI_GEMM_STAMP") != nullptr;
   // unconditional weight loads (ULD) whenever NTW % 4 != 0 (gate/up T = 168:
   // 55.9 -> 51.2 us, qkv 37.2 -> 34.6 us in scripts/gemm_bench.py);
@@ -1197,7 +1210,7 @@ static hipError_t run_mid(const uint16_t *X, const uint16_t *Wp, uint16_t *Y, fl
   const bool ntl = nt && mblocks == 1;
 #define FFMI_MID2(E, ST, XPK, U, NL)                                                               \
   hipLaunchKernelGGL((gemm_mid_kernel<MTW, NTW, PF, E, ST, XPK, U, NL>), grid, dim3(256), 0, s, X, \
-                     Wp, Y, ws, T, N, K, KT, ntiles, S, yp, wts, wks)
+                     Wp, Y, ws, T, N, K, KT, ntiles, S, yp, wts, wks, xmap)
 #define FFMI_MID(E, ST, XPK)                                  \
   do {                                                        \
     const bool u_ = uld && NTW % 4;                           \
