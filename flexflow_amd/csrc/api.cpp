@@ -1152,6 +1152,14 @@ extern "C" long ffmi_debug_gemm_stamps(long long *dst, long max_waves) {
   return ffmi::gemm_debug_stamps(dst, max_waves);
 }
 
+extern "C" ffmi_status ffmi_debug_gemm_plan(int T, int out_dim, int in_dim, int epilogue,
+                                            int *plan) {
+  FFMI_CHECK(plan && T > 0 && out_dim > 0, FFMI_ERR_INVALID);
+  FFMI_CHECK(in_dim > 0 && in_dim % 32 == 0, FFMI_ERR_UNSUPPORTED);
+  ffmi::gemm_debug_plan(T, out_dim, in_dim, epilogue, plan);
+  return FFMI_OK;
+}
+
 extern "C" long ffmi_debug_attn_stamps(long long *dst, long max_waves) {
   return ffmi::attn_debug_stamps(dst, max_waves);
 }

@@ -619,6 +619,13 @@ static hipError_t dispatch_fused(const uint16_t *X, const uint16_t *Wp, uint16_t
   return run<MT, 1, 4, U, 0, FZ>(X, Wp, Y, nullptr, T, N, K, KT, ntiles, 1, s, xp, yp, nt, wpitch, fz);
 }
 
+// Wide, short-K layers of the skinny range (T <= 64) take gemm_wave_kernel
+// (FFMI_WAVE_GEMM=0 keeps the K-split form); dispatch_nt and gemm_path.
+static bool wave_form(int N, int KT, int epi, int S) {
+  static const bool wave_ok = !getenv("FFMI_WAVE_GEMM") || atoi(getenv("FFMI_WAVE_GEMM")) != 0;
+  return wave_ok && !epi && (N + 15) / 16 >= 1024 && KT <= 32 && S == 1;
+}
+
 template <int MT, int U>
 static hipError_t dispatch_nt(const uint16_t *X, const uint16_t *Wp, uint16_t *Y, float *ws,
                               int T, int N, int K, int KT, int epi, int S, hipStream_t s,
@@ -644,9 +651,8 @@ static hipError_t dispatch_nt(const uint16_t *X, const uint16_t *Wp, uint16_t *Y
     if (fnt == 2 && fkw == 2) return run<MT, 2, 2, U, 0>(X, Wp, Y, ws, T, N, K, KT, ntiles, 1, s, xp, yp, nt, wpitch);
   }
   // wide, short-K layers (the SSM lm_head): one wave per 2 tiles over the
-  // whole K (gemm_wave_kernel; FFMI_WAVE_GEMM=0 keeps the K-split form)
-  static const bool wave_ok = !getenv("FFMI_WAVE_GEMM") || atoi(getenv("FFMI_WAVE_GEMM")) != 0;
-  if (wave_ok && ntiles >= 1024 && KT <= 32 && S == 1) {
+  // whole K (gemm_wave_kernel)
+  if (wave_form(N, KT, epi, S)) {
     const size_t wts = w_tile_stride(KT), wks = w_k_stride(wpitch);
     // two tiles per wave: SSM lm_head (32000 x 768) at T = 24 11.1 us (13.3
     // in the K-split form, 13.3 with one tile per wave and twice the waves),
@@ -1142,8 +1148,9 @@ static MidPlan mid_plan(int T, int N, int K, int epi, bool deferred = false) {
     }
   }
   // diagnostics: FFMI_GEMM_PLAN="NTW,S" forces the tile width and split of
-  // every M-split launch; "N:K:NTW,S;..." only of the listed shapes
-  static const char *force = getenv("FFMI_GEMM_PLAN");
+  // every M-split launch; "N:K:NTW,S;..." only of the listed shapes (A/B
+  // runs and tests; read per call)
+  const char *force = getenv("FFMI_GEMM_PLAN");
   if (force) {
     const char *q = force;
     while (q && *q) {
@@ -1163,6 +1170,30 @@ static MidPlan mid_plan(int T, int N, int K, int epi, bool deferred = false) {
   if (p.MTW == 4 && p.NTW > 8) p.NTW = 8;
   p.nblk = (ntiles + p.NTW - 1) / p.NTW;
   return p;
+}
+
+// Launch form of an unfused GEMM (epi without the layout flags): what
+// launch_gemm dispatches on and gemm_debug_plan reports.
+enum { GEMM_SKINNY = 0, GEMM_WAVE = 1, GEMM_MID = 2, GEMM_TILE = 3 };
+static int gemm_path(int T, int N, int K, int epi, bool xp, bool deferrable) {
+  const int mtiles = (T + 15) / 16;
+  // prefill blocks: the compute-bound 256 x 256 tile form where its grid
+  // covers the CUs (FFMI_TILE_GEMM: 0 never, 2 whenever the shape allows --
+  // A/B runs and tests; read per call)
+  if (mtiles >= 32 && xp) {
+    const char *e = getenv("FFMI_TILE_GEMM");
+    const int mode = e ? atoi(e) : 1;
+    const int ntiles = (N + 15) / 16 * (epi ? 2 : 1);
+    const int nbn = (ntiles + 15) / 16, nbm = (mtiles + 15) / 16;
+    // one 256 x 256 tile per CU and round: worth it where the rounds are
+    // well filled (T = 1024: qkv 192 tiles 168 -> 140 us, lm_head 500 tiles
+    // 396 -> 314, gate/up 344 tiles 274 -> 268; T = 577: gate/up's 258 tiles
+    // = one round + 2, 188 -> 221, stays M-split)
+    const int nwg = nbn * nbm, rounds = (nwg + 255) / 256;
+    if (mode == 2 || (mode == 1 && nwg >= 160 && nwg * 10 >= rounds * 256 * 6)) return GEMM_TILE;
+  }
+  if (mtiles > 4) return GEMM_MID;
+  return wave_form(N, K / 32, epi, skinny_split(T, N, K, epi, deferrable)) ? GEMM_WAVE : GEMM_SKINNY;
 }
 
 size_t gemm_workspace_bytes(int T, int N, int K, int epilogue) {
@@ -1308,32 +1339,20 @@ hipError_t launch_gemm(const uint16_t *X, const uint16_t *Wp, uint16_t *Y, float
     FFMI_FZ(2, 2);
 #undef FFMI_FZ
   }
-  // prefill blocks: the compute-bound 256 x 256 tile form where its grid
-  // covers the CUs (FFMI_TILE_GEMM: 0 never, 2 whenever the shape allows --
-  // A/B runs and tests; read per call)
-  if (mtiles >= 32 && xp && (!fuse || !fuse->kind)) {
-    const char *e = getenv("FFMI_TILE_GEMM");
-    const int mode = e ? atoi(e) : 1;
+  const int path = gemm_path(T, N, K, epilogue, xp, defer != nullptr);
+  if (path == GEMM_TILE) {
     const int ntiles = (N + 15) / 16 * (epilogue ? 2 : 1);
     const int nbn = (ntiles + 15) / 16, nbm = (mtiles + 15) / 16;
-    // one 256 x 256 tile per CU and round: worth it where the rounds are
-    // well filled (T = 1024: qkv 192 tiles 168 -> 140 us, lm_head 500 tiles
-    // 396 -> 314, gate/up 344 tiles 274 -> 268; T = 577: gate/up's 258 tiles
-    // = one round + 2, 188 -> 221, stays M-split)
-    const int nwg = nbn * nbm, rounds = (nwg + 255) / 256;
-    if (mode == 2 || (mode == 1 && nwg >= 160 && nwg * 10 >= rounds * 256 * 6)) {
-      if (defer) defer->S = 0;
-      const size_t wts = w_tile_stride(KT), wks = w_k_stride(wpitch ? wpitch : ntiles);
-      if (epilogue)
-        hipLaunchKernelGGL((gemm_tile_kernel<1, 4>), dim3(nbn * nbm), dim3(512), 0, s, X, Wp, Y, T,
-                           N, KT, ntiles, mtiles, nbm, yp, wts, wks);
-      else
-        hipLaunchKernelGGL((gemm_tile_kernel<0, 4>), dim3(nbn * nbm), dim3(512), 0, s, X, Wp, Y, T,
-                           N, KT, ntiles, mtiles, nbm, yp, wts, wks);
-      return hipGetLastError();
-    }
+    const size_t wts = w_tile_stride(KT), wks = w_k_stride(wpitch ? wpitch : ntiles);
+    if (epilogue)
+      hipLaunchKernelGGL((gemm_tile_kernel<1, 4>), dim3(nbn * nbm), dim3(512), 0, s, X, Wp, Y, T,
+                         N, KT, ntiles, mtiles, nbm, yp, wts, wks);
+    else
+      hipLaunchKernelGGL((gemm_tile_kernel<0, 4>), dim3(nbn * nbm), dim3(512), 0, s, X, Wp, Y, T,
+                         N, KT, ntiles, mtiles, nbm, yp, wts, wks);
+    return hipGetLastError();
   }
-  if (mtiles > 4) {
+  if (path == GEMM_MID) {
     const MidPlan p = mid_plan(T, N, K, epilogue, defer != nullptr && !epilogue);
 #define FFMI_RUN(M, NW) \
   return run_mid<M, NW, 4>(X, Wp, Y, ws, ws_bytes, T, N, K, epilogue, s, xp, yp, p.S, defer, nt, \
@@ -1391,6 +1410,21 @@ hipError_t launch_pack_act(const uint16_t *X, uint16_t *Xp, int T, int K, hipStr
   hipLaunchKernelGGL(pack_act_kernel, dim3(K / 32, (T + 15) / 16), dim3(64), 0, s, X, Xp, T, K,
                      K / 32);
   return hipGetLastError();
+}
+
+// diagnostics: {path, MTW, NTW, S, mblocks, nblk} of the launch launch_gemm
+// makes for these arguments without a deferred consumer (ffmi_linear); the
+// last five describe the M-split grid and are 0, 0, 1, 0, 0 on the other
+// paths.  Host only: no launch, no device.
+void gemm_debug_plan(int T, int N, int K, int epilogue, int *plan) {
+  const bool xp = (epilogue & FFMI_X_PACKED) != 0;
+  epilogue &= ~(FFMI_X_PACKED | FFMI_Y_PACKED | FFMI_W_STREAM);
+  plan[0] = gemm_path(T, N, K, epilogue, xp, false);
+  plan[1] = plan[2] = plan[4] = plan[5] = 0;
+  plan[3] = 1;
+  if (plan[0] != GEMM_MID) return;
+  const MidPlan p = mid_plan(T, N, K, epilogue, false);
+  plan[1] = p.MTW, plan[2] = p.NTW, plan[3] = p.S, plan[4] = p.mblocks, plan[5] = p.nblk;
 }
 
 // diagnostics: stamps of the last FFMI_GEMM_STAMP launch (8 int64 per wave)

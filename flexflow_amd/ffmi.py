@@ -210,6 +210,7 @@ SIGNATURES = {
                                 c_float, c_int, c_void_p]),
     "ffmi_pack_activations": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "ffmi_debug_gemm_stamps": (ctypes.c_long, [c_void_p, ctypes.c_long]),
+    "ffmi_debug_gemm_plan": (c_int, [c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)]),
     "ffmi_debug_fused_residual_linear": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                                  c_int, c_int, c_void_p]),
     "ffmi_debug_fused_norm_linear": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_void_p,

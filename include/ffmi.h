@@ -596,6 +596,14 @@ ffmi_status ffmi_debug_fused_norm_linear(const void *residual, const float *ss_i
  * ({start, prologue done, k-loop done, end} at 100 MHz, HW_ID, XCC_ID) and
  * returns the number of waves (<= max_waves). */
 long ffmi_debug_gemm_stamps(long long *dst, long max_waves);
+/* Test hook: the launch ffmi_linear makes for these arguments (epilogue with
+ * its layout flags), as plan = {path, MTW, NTW, S, mblocks, nblk}: path 0
+ * skinny, 1 wave, 2 M-split, 3 the 256 x 256 tile form; row tiles per wave,
+ * weight tiles per workgroup, split-K slices, row blocks and tile blocks of an
+ * M-split launch (0, 0, 1, 0, 0 on the other paths).  FFMI_GEMM_PLAN is
+ * honoured; the A/B-only forced skinny / wave forms are not reported.
+ * Launches nothing and needs no device. */
+ffmi_status ffmi_debug_gemm_plan(int T, int out_dim, int in_dim, int epilogue, int *plan /* [6] */);
 /* Diagnostics: per-wave timeline of the last verify-size attention launch when
  * FFMI_ATTN_STAMP=1 (12 int64 per wave: start, after prologue, before the key
  * loop, after it, after the merge barrier, end, then [one-launch path] after

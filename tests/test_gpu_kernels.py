@@ -204,6 +204,29 @@ def flip_bound(rate, n):
     return 1.0 - max(2.0, rate * n + 3.0 * np.sqrt(rate * n)) / n
 
 
+def silu_box_check(y, g, u, ctx=None):
+    """the gate/up box check of test_gpu_llama_shapes, for a SiLU-mul GEMM
+    result y against the oracle's fp32 gate and up products: >= 98% bit-
+    identical to the chain on the oracle's fp16 gate/up, the rest inside the
+    chain's range over gate/up within the plain GEMM tolerance (a one-ulp
+    flip of g near silu's flat region moves y by several ulps) + 1 output
+    ulp.  Returns the bit-identical fraction."""
+    g16, u16 = g.astype(np.float16), u.astype(np.float16)
+    chain = lambda a, b: O.silu_mul(a.astype(np.float32), b.astype(np.float32))  # noqa: E731
+    y16 = y.astype(np.float16)
+    exact = (y16 == chain(g16, u16).astype(np.float16)).mean()
+    assert exact >= flip_bound(0.02, y.size), (exact, ctx)
+    sp = lambda a: np.spacing(np.abs(a).astype(np.float16)).astype(np.float32)  # noqa: E731
+    dg = np.maximum(2 * sp(g16), 1e-4 * np.abs(g).max())
+    du = np.maximum(2 * sp(u16), 1e-4 * np.abs(u).max())
+    pts = [chain(g + a * dg, u + b * du) for a in (-1, 0, 1) for b in (-1, 0, 1)]
+    lo, hi = np.min(pts, axis=0), np.max(pts, axis=0)
+    slack = sp(np.maximum(np.abs(lo), np.abs(hi)))
+    yf = y16.astype(np.float32)
+    assert not ((yf < lo - slack) | (yf > hi + slack)).any(), ctx
+    return float(exact)
+
+
 @pytest.mark.parametrize("seed", range(20 * RS))
 def test_linear_random_shapes_vs_oracle(seed):
     """ffmi_linear at random shapes against the oracle: T 1-1100 (skinny,
@@ -241,23 +264,7 @@ def test_linear_random_shapes_vs_oracle(seed):
         if epi:
             g = O.linear(X.astype(np.float32), Wg.astype(np.float32))
             u = O.linear(X.astype(np.float32), Wu.astype(np.float32))
-            # the gate/up box check of test_gpu_llama_shapes: >= 98% bit-
-            # identical to the chain on the oracle's fp16 gate/up, the rest
-            # inside the chain's range over gate/up within the plain GEMM
-            # tolerance (a one-ulp flip of g near silu's flat region moves y
-            # by several ulps) + 1 output ulp
-            g16, u16 = g.astype(np.float16), u.astype(np.float16)
-            chain = lambda a, b: O.silu_mul(a.astype(np.float32), b.astype(np.float32))  # noqa: E731
-            y16 = y.astype(np.float16)
-            assert (y16 == chain(g16, u16).astype(np.float16)).mean() >= flip_bound(0.02, y.size)
-            sp = lambda a: np.spacing(np.abs(a).astype(np.float16)).astype(np.float32)  # noqa: E731
-            dg = np.maximum(2 * sp(g16), 1e-4 * np.abs(g).max())
-            du = np.maximum(2 * sp(u16), 1e-4 * np.abs(u).max())
-            pts = [chain(g + a * dg, u + b * du) for a in (-1, 0, 1) for b in (-1, 0, 1)]
-            lo, hi = np.min(pts, axis=0), np.max(pts, axis=0)
-            slack = sp(np.maximum(np.abs(lo), np.abs(hi)))
-            yf = y16.astype(np.float32)
-            assert not ((yf < lo - slack) | (yf > hi + slack)).any(), (T, N, K, flags)
+            silu_box_check(y, g, u, (T, N, K, flags))
         else:  # (>= 99% bit-identical, with the binomial margin of a small output)
             close16(y, O.linear(X.astype(np.float32), W.astype(np.float32), fp16=1),
                     exact_frac=flip_bound(0.01, y.size))
