@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/ffmi.h"
+#include "kernels/gemm_plan.h"
 
 #define FFMI_HIP(expr)                                   \
   do {                                                   \
@@ -215,8 +216,7 @@ struct FuseArgs {
 hipError_t launch_gemm(const uint16_t *X, const uint16_t *Wp, uint16_t *Y, float *ws,
                        size_t ws_bytes, int T, int N, int K, int epilogue, hipStream_t s,
                        Partials *defer = nullptr, int wpitch = 0, const FuseArgs *fuse = nullptr);
-size_t gemm_workspace_bytes(int T, int N, int K, int epilogue);
-void gemm_debug_plan(int T, int N, int K, int epilogue, int *plan /* [6] */);
+// (gemm_workspace_bytes, gemm_debug_plan: kernels/gemm_plan.h)
 // fp16 Y[T][N] (row-major) of deferred split-K slabs, summed in slab order and
 // rounded once: the value every consumer of the slabs computes (tensor capture)
 hipError_t launch_partials_reduce(const Partials &p, uint16_t *Y, int T, int N, hipStream_t s);

@@ -20,12 +20,8 @@
 //    row's result does not depend on T or on which other rows are batched.
 // Epilogue FFMI_EPI_SILU_MUL fuses SigmoidSiluMulti (sigmoid_silu_multi.cu:
 // 37-47) on interleaved [gate|up] tiles.
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <algorithm>
 #include <type_traits>
+#include <utility>
 
 #include "../ffmi_internal.h"
 
@@ -74,6 +70,7 @@ __device__ __forceinline__ float lane_f(float v, int l) {
 // unsplit), 2 = RMSNorm consumer prologue on row-major X.  Y is restrict-
 // qualified except in the producer, where it aliases fz.res_in (the residual
 // is updated in place).
+// (instantiated for kRowTiles x kSkinnyForms, gemm_plan.h)
 template <int FZ>
 using SkinnyY = std::conditional_t<FZ == 1, uint16_t *, uint16_t *__restrict__>;
 template <int MT, int NT, int KW, int U, int EPI, bool PIPE = false, bool NTL = false, int FZ = 0>
@@ -455,42 +452,13 @@ __global__ __launch_bounds__(KW * 64) void gemm_skinny_kernel(
   }
 }
 
-template <int MT, int NT, int KW, int U, int EPI, int FZ = 0>
-static hipError_t run(const uint16_t *X, const uint16_t *Wp, uint16_t *Y, float *ws, int T,
-                      int N, int K, int KT, int NTILES, int S, hipStream_t s, int xp, int yp,
-                      bool nt, int wpitch, const FuseArgs &fz = FuseArgs()) {
-  const size_t wts = w_tile_stride(KT), wks = w_k_stride(wpitch);
-  const int ncb = (NTILES + NT - 1) / NT;
-  dim3 grid(ncb, S);
-  size_t lds = KW > 1 ? (size_t)(KW - 1) * MT * NT * 4 * 64 * sizeof(float) : 0;
-  // software-pipelined k-loop once every wave has >= 2 full batches (LLaMA-7B
-  // decode at T = 8, cold: qkv 21.2 -> 19.5 us, gate/up 39.1 -> 36.8, lm_head
-  // 49.5 -> 46.1); short loops (the SSM, K = 768) keep the batched form, which
-  // the pipeline slowed (SSM lm_head warm 9.3 -> 12.1 us).
-  // FFMI_SKINNY_PIPE=0/1 forces it off/on (A/B runs).
-  static const int force = getenv("FFMI_SKINNY_PIPE") ? atoi(getenv("FFMI_SKINNY_PIPE")) : -1;
-  const int per_wave = ((KT + S - 1) / S + KW - 1) / KW;
-  const bool pipe = force >= 0 ? force != 0 : per_wave >= 2 * U;
-#define FFMI_SKINNY_LAUNCH(PP, NL)                                                             \
-  hipLaunchKernelGGL((gemm_skinny_kernel<MT, NT, KW, U, EPI, PP, NL, FZ>), grid, dim3(KW * 64), \
-                     lds, s, X, Wp, Y, ws, T, N, K, KT, NTILES, xp, yp, wts, wks, fz)
-  if (pipe) {
-    if (nt) FFMI_SKINNY_LAUNCH(true, true);
-    else FFMI_SKINNY_LAUNCH(true, false);
-  } else {
-    if (nt) FFMI_SKINNY_LAUNCH(false, true);
-    else FFMI_SKINNY_LAUNCH(false, false);
-  }
-#undef FFMI_SKINNY_LAUNCH
-  return hipGetLastError();
-}
-
 // Wide, short-K layers (the 68M SSM's lm_head: 2000 tiles, K = 768): one
 // WAVE per group of NT tiles over the whole K (a single MFMA chain per tile,
 // no cross-wave reduction, no LDS), four independent waves per workgroup.
 // The K-split form launches 1000 short 4-wave workgroups whose loads never
 // fill the CU (13 us for 49 MB from the Infinity Cache); here each wave keeps
 // two batches of UB k-steps in flight (double-buffered registers).
+// (instantiated for kRowTiles x kWaveForms, gemm_plan.h)
 template <int MT, int NT, int UB, bool NTL, int WPG = 4>
 __global__ __launch_bounds__(WPG * 64) void gemm_wave_kernel(const uint16_t *__restrict__ X,
                                                              const uint16_t *__restrict__ Wp,
@@ -572,142 +540,6 @@ __global__ __launch_bounds__(WPG * 64) void gemm_wave_kernel(const uint16_t *__r
   }
 }
 
-// Split-K factor of the skinny path: only narrow layers (few column groups,
-// e.g. the 68M SSM's o/down with 48 tiles) and only when the consumer takes
-// the partial slabs (no reduce pass); keeps >= 4 k-steps per wave.
-static int skinny_split(int T, int N, int K, int epi, bool deferrable) {
-  // FFMI_SKINNY_SPLIT=0 keeps every skinny launch unsplit (A/B runs)
-  static const bool off = getenv("FFMI_SKINNY_SPLIT") && atoi(getenv("FFMI_SKINNY_SPLIT")) == 0;
-  if (off || !deferrable || epi || T > 64) return 1;
-  const int ntiles = (N + 15) / 16;
-  if (ntiles >= 128) return 1;
-  const int KT = K / 32;
-  int S = 256 / ntiles;
-  S = std::min(S, std::max(1, KT / 8));  // >= 1 k-step per wave of an 8-wave slice
-  return std::max(1, std::min(S, 8));
-}
-
-// The fused residual/norm forms (FuseArgs; S == 1, T <= 32): the unfused
-// path's tile and wave choices, one instantiation set per role.
-template <int MT, int U, int FZ>
-static hipError_t dispatch_fused(const uint16_t *X, const uint16_t *Wp, uint16_t *Y, int T, int N,
-                                 int K, int KT, int epi, hipStream_t s, int xp, int yp, bool nt,
-                                 int wpitch, const FuseArgs &fz) {
-  const int ntiles = (N + 15) / 16;
-  // FFMI_FZ_KW8 (A/B): 8 K-split waves instead of 4 for the one-row-tile
-  // consumer launches -- 1: qkv, 2: qkv and gate/up
-  static const int kw8 = getenv("FFMI_FZ_KW8") ? atoi(getenv("FFMI_FZ_KW8")) : 0;
-  if (epi == FFMI_EPI_SILU_MUL) {
-    if constexpr (FZ == 2) {
-      if (kw8 >= 2 && MT == 1)
-        return run<MT, 2, 8, U, 1, 2>(X, Wp, Y, nullptr, T, N, K, KT, 2 * ntiles, 1, s, xp, yp, nt,
-                                      wpitch, fz);
-      return run<MT, 2, 4, U, 1, 2>(X, Wp, Y, nullptr, T, N, K, KT, 2 * ntiles, 1, s, xp, yp, nt,
-                                    wpitch, fz);
-    }
-    return hipErrorInvalidValue;
-  }
-  if constexpr (FZ == 2)
-    if (kw8 >= 1 && MT == 1 && ntiles >= 512)
-      return run<MT, 1, 8, U, 0, FZ>(X, Wp, Y, nullptr, T, N, K, KT, ntiles, 1, s, xp, yp, nt, wpitch, fz);
-  // FFMI_FZ_NT2=1: two tiles per workgroup at one row tile too (A/B)
-  static const bool nt2 = getenv("FFMI_FZ_NT2") && atoi(getenv("FFMI_FZ_NT2")) != 0;
-  if ((MT >= 2 || nt2) && ntiles >= 512)
-    return run<MT, 2, 4, U, 0, FZ>(X, Wp, Y, nullptr, T, N, K, KT, ntiles, 1, s, xp, yp, nt, wpitch, fz);
-  if (ntiles < 512 && KT >= 64 && !nt)
-    return run<MT, 1, 8, U, 0, FZ>(X, Wp, Y, nullptr, T, N, K, KT, ntiles, 1, s, xp, yp, nt, wpitch, fz);
-  return run<MT, 1, 4, U, 0, FZ>(X, Wp, Y, nullptr, T, N, K, KT, ntiles, 1, s, xp, yp, nt, wpitch, fz);
-}
-
-// Wide, short-K layers of the skinny range (T <= 64) take gemm_wave_kernel
-// (FFMI_WAVE_GEMM=0 keeps the K-split form); dispatch_nt and gemm_path.
-static bool wave_form(int N, int KT, int epi, int S) {
-  static const bool wave_ok = !getenv("FFMI_WAVE_GEMM") || atoi(getenv("FFMI_WAVE_GEMM")) != 0;
-  return wave_ok && !epi && (N + 15) / 16 >= 1024 && KT <= 32 && S == 1;
-}
-
-template <int MT, int U>
-static hipError_t dispatch_nt(const uint16_t *X, const uint16_t *Wp, uint16_t *Y, float *ws,
-                              int T, int N, int K, int KT, int epi, int S, hipStream_t s,
-                              int xp, int yp, bool nt, int wpitch) {
-  int ntiles = (N + 15) / 16;
-  if (!wpitch) wpitch = epi == FFMI_EPI_SILU_MUL ? 2 * ntiles : ntiles;
-  if (epi == FFMI_EPI_SILU_MUL)
-    return run<MT, 2, 4, U, 1>(X, Wp, Y, ws, T, N, K, KT, 2 * ntiles, 1, s, xp, yp, nt, wpitch);
-  // diagnostics: FFMI_SKINNY="NT,KW" forces the tile count and K-split waves
-  // of every unsplit skinny launch (A/B runs, scripts/gemm_bench.py)
-  static int fnt = -1, fkw = 0;
-  if (fnt < 0) {
-    fnt = 0;
-    if (const char *e = getenv("FFMI_SKINNY")) (void)sscanf(e, "%d,%d", &fnt, &fkw);
-  }
-  if (fnt > 0 && S == 1 && MT <= 2) {
-    if (fnt == 1 && fkw == 4) return run<MT, 1, 4, U, 0>(X, Wp, Y, ws, T, N, K, KT, ntiles, 1, s, xp, yp, nt, wpitch);
-    if (fnt == 1 && fkw == 8) return run<MT, 1, 8, U, 0>(X, Wp, Y, ws, T, N, K, KT, ntiles, 1, s, xp, yp, nt, wpitch);
-    if (fnt == 2 && fkw == 4) return run<MT, 2, 4, U, 0>(X, Wp, Y, ws, T, N, K, KT, ntiles, 1, s, xp, yp, nt, wpitch);
-    if (fnt == 2 && fkw == 8) return run<MT, 2, 8, U, 0>(X, Wp, Y, ws, T, N, K, KT, ntiles, 1, s, xp, yp, nt, wpitch);
-    if (fnt == 4 && fkw == 4) return run<MT, 4, 4, U, 0>(X, Wp, Y, ws, T, N, K, KT, ntiles, 1, s, xp, yp, nt, wpitch);
-    if (fnt == 4 && fkw == 2) return run<MT, 4, 2, U, 0>(X, Wp, Y, ws, T, N, K, KT, ntiles, 1, s, xp, yp, nt, wpitch);
-    if (fnt == 2 && fkw == 2) return run<MT, 2, 2, U, 0>(X, Wp, Y, ws, T, N, K, KT, ntiles, 1, s, xp, yp, nt, wpitch);
-  }
-  // wide, short-K layers (the SSM lm_head): one wave per 2 tiles over the
-  // whole K (gemm_wave_kernel)
-  if (wave_form(N, KT, epi, S)) {
-    const size_t wts = w_tile_stride(KT), wks = w_k_stride(wpitch);
-    // two tiles per wave: SSM lm_head (32000 x 768) at T = 24 11.1 us (13.3
-    // in the K-split form, 13.3 with one tile per wave and twice the waves),
-    // T = 8 9.4 us (12.5)
-    // (FFMI_WAVE_FORM=NT,WPG: tiles per wave and waves per workgroup, A/B)
-    static int wnt = 2, wpg = 4;
-    static bool wread = false;
-    if (!wread) {
-      wread = true;
-      if (const char *e = getenv("FFMI_WAVE_FORM")) (void)sscanf(e, "%d,%d", &wnt, &wpg);
-    }
-#define FFMI_WAVE(NTV, WPGV, NL)                                                               \
-  hipLaunchKernelGGL((gemm_wave_kernel<MT, NTV, 4, NL, WPGV>),                                 \
-                     dim3(((ntiles + NTV - 1) / NTV + WPGV - 1) / WPGV), dim3(WPGV * 64), 0, s, X, \
-                     Wp, Y, T, N, KT, ntiles, xp, yp, wts, wks)
-    if (wnt == 4 && wpg == 2) {
-      if (nt) FFMI_WAVE(4, 2, true);
-      else FFMI_WAVE(4, 2, false);
-    } else if (wnt == 4 && wpg == 4) {
-      if (nt) FFMI_WAVE(4, 4, true);
-      else FFMI_WAVE(4, 4, false);
-    } else if (wnt == 3 && wpg == 2) {
-      if (nt) FFMI_WAVE(3, 2, true);
-      else FFMI_WAVE(3, 2, false);
-    } else if (wnt == 2 && wpg == 2) {
-      if (nt) FFMI_WAVE(2, 2, true);
-      else FFMI_WAVE(2, 2, false);
-    } else {
-      if (nt) FFMI_WAVE(2, 4, true);
-      else FFMI_WAVE(2, 4, false);
-    }
-#undef FFMI_WAVE
-    return hipGetLastError();
-  }
-  // wide layers (lm_head): two tiles per workgroup once there are >= 2 row
-  // tiles (SSM lm_head at T = 24: 16.1 -> 12.3 us warm; at one row tile a
-  // single tile stays faster: LLaMA-7B lm_head T = 8 cold 47.8 vs 55.8 us)
-  if (MT >= 2 && ntiles >= 512)
-    return run<MT, 2, 4, U, 0>(X, Wp, Y, ws, T, N, K, KT, ntiles, S, s, xp, yp, nt, wpitch);
-  // 8-wave groups only where the accumulators fit 2 waves/SIMD (no spills)
-  if (ntiles >= 512 || MT >= 8)
-    return run<MT, 1, 4, U, 0>(X, Wp, Y, ws, T, N, K, KT, ntiles, S, s, xp, yp, nt, wpitch);
-  // ... and where each wave still gets a full batch of U k-steps (K = 768 of
-  // the SSM: 4 waves x 6 k-steps beat 8 x 3, qkv T = 24: 5.7 -> 4.2 us).
-  // Non-temporal weight loads (FFMI_W_STREAM) keep 4 waves at every row-tile
-  // count (LLaMA-7B decode, cold, T = 1-16: o 7.6-8.8 -> 7.2-8.6 us, down
-  // 17.0-24.8 -> 16.4-21.9 us over two runs of gemm_bench.py --wstream; T = 32
-  // within noise), so a row's reduction order still depends on (N-tile, K,
-  // policy) only, not on T: the threshold is a fixed 64 k-steps per slice
-  // (8 waves x the largest batch U = 8), never U itself, which depends on T.
-  if ((KT + S - 1) / S >= 64 && !nt)
-    return run<MT, 1, 8, U, 0>(X, Wp, Y, ws, T, N, K, KT, ntiles, S, s, xp, yp, nt, wpitch);
-  return run<MT, 1, 4, U, 0>(X, Wp, Y, ws, T, N, K, KT, ntiles, S, s, xp, yp, nt, wpitch);
-}
-
 // ---------------------------------------------------------------------------
 // M-split GEMM for 64 < T (verify batches, SSM init, prefill blocks).
 //
@@ -786,6 +618,7 @@ __device__ __forceinline__ void mid_store(const f4 (&acc)[MTW][NTW], uint16_t *_
 __device__ long long *g_gemm_stamps;
 __device__ __forceinline__ long long rt_now() { return __builtin_amdgcn_s_memrealtime(); }
 
+// (instantiated for kMidShapes, gemm_plan.h)
 template <int MTW, int NTW, int PF, int EPI, bool STAMP = false, bool XP = false, bool ULD = false,
           bool NTL = false>
 // (two workgroups per CU = 256 registers per wave: up to 24 accumulator tiles,
@@ -1029,6 +862,7 @@ static long g_stamp_entries = 0;
 
 // Sum the S fp32 partial slabs in slice order, then the epilogue; one thread
 // per 4 consecutive output columns (16-B slab loads, 8-B fp16 store).
+// (instantiated for kReduceMaxS, gemm_plan.h)
 template <int EPI, int MAXS>
 __global__ void gemm_reduce_kernel(const float *__restrict__ Ypart, uint16_t *__restrict__ Y,
                                    int T, int N, int NTILES, int S, int yp) {
@@ -1072,239 +906,54 @@ __global__ void gemm_reduce_kernel(const float *__restrict__ Ypart, uint16_t *__
   }
 }
 
-// Launch plan of the M-split kernel: weight tiles per workgroup (NTW) and
-// split-K factor (S).  Each workgroup is bound by its CU's load path (per-wave
-// timeline, scripts/diag_stamps.py: a k-step moves NTW KiB of weights + 4*MTW
-// KiB of activations at ~50 GB/s per CU; two workgroups on one CU each run at
-// half speed), so the plan keeps the grid within one wave of 256 workgroups,
-// prefers wide tiles (fewer activation bytes per weight byte) and charges the
-// split-K reduce pass.  Times in us; only the ranking matters.
-struct MidPlan {
-  int MTW, NTW, S, mblocks, nblk;
-};
-// FFMI_MID_MTW4=0: no 4-row-tile waves (A/B)
-static const int mid_mtw4 = getenv("FFMI_MID_MTW4") && atoi(getenv("FFMI_MID_MTW4")) == 0 ? 3 : 4;
-static MidPlan mid_plan(int T, int N, int K, int epi, bool deferred = false) {
-  MidPlan p;
-  const int mtiles = (T + 15) / 16;
-  // row tiles per wave: 4 waves x MTW tiles cover one row block; 4 for 13-16
-  // tiles (T 193-256: the width-4 verify step, T = 216, in ONE row block
-  // instead of two that each re-read every weight tile) and for prefill
-  // blocks (fewer row blocks re-reading the weights)
-  p.MTW = mtiles <= 8 ? 2 : mtiles <= 12 ? 3 : mtiles <= 16 || mtiles > 24 ? mid_mtw4 : 3;
-  p.mblocks = (mtiles + 4 * p.MTW - 1) / (4 * p.MTW);
-  const int KT = K / 32;
-  const int ntiles = (N + 15) / 16 * (epi ? 2 : 1);
-  double best = 1e30;
-  p.NTW = 8, p.S = 1;
-  // measured k-step times (us) at MTW = 3, packed activations (diag_stamps.py)
-  // (2 and 4: narrow per-rank shards of tensor parallelism, e.g. LLaMA-7B
-  // o_proj at TP = 8 is 256 tiles x K = 512 -- 43 workgroups at NTW = 6)
-  static const int ntw_opts[6] = {2, 4, 6, 8, 12, 16};
-  static const double base[6] = {0.27, 0.30, 0.36, 0.40, 0.65, 0.90};
-  static const int nopt = getenv("FFMI_MID_NARROW") && atoi(getenv("FFMI_MID_NARROW")) == 0 ? 4 : 6;
-  for (int o = 6 - nopt; o < 6; ++o) {
-    const int ntw = ntw_opts[o];
-    if (p.MTW == 4 && ntw > 8) continue;  // (register budget, see launch_gemm)
-    const int nblk = (ntiles + ntw - 1) / ntw;
-    for (int S = 1; S <= 8 && S <= KT; ++S) {
-      const long wgs = (long)nblk * S * p.mblocks;
-      const double rounds = (double)((wgs + 255) / 256);
-      const double steps = (double)((KT + S - 1) / S);
-      const double tstep = base[o] * (ntw + 4.0 * p.MTW) / (ntw + 12.0);
-      double t = rounds * (steps * tstep + 4.0);
-      const double slab_mb = (double)S * T * ntiles * 16 * 4 / 1e6;
-      // slabs cost their write here and their read in the consumer; a
-      // deferred read (norm / attention prologue) is no cheaper than the
-      // reduce pass's: /6 had picked 8 slabs for LLaMA-7B o_proj at T = 168,
-      // 4 tiles x 4 slabs ran 0.6 % faster end to end (3 of 3 A/B pairs)
-      // (the SiLU reduce pass re-reads the gate AND up slabs: at the verify
-      // size, 9-12 row tiles in one block, a forced-plan sweep of the TP = 8
-      // gate/up shard put 4 tiles x 4-5 slabs at 18.4-18.9 us against 21.7
-      // for the 6 x 8 the /3 charge picked, profiles/r06_tp8_gateup_plans.log;
-      // the TP 1 / 2 / 4 and 65B TP 8 picks are unchanged by /2)
-      const double slab_rate = epi && p.MTW == 3 && p.mblocks == 1 ? 2.0 : 3.0;
-      if (S > 1) t += deferred ? slab_mb / 3.0 : 3.0 + slab_mb / slab_rate;
-      if (t < best - 1e-9) best = t, p.NTW = ntw, p.S = S;
-    }
-  }
-  // prefill blocks (>= 4 row blocks: T > 576 at MTW = 3): the k-step model
-  // above is calibrated at T = 168; forced-plan sweeps at T = 1024
-  // (scripts/gpu_prefill_plans.sh, LLaMA-7B shapes) put 8 tiles unsplit
-  // first on qkv / o / gate-up / lm_head and 8 tiles x 2 slices on the
-  // K = 11008 down projection (gate/up 337 -> 270 us, qkv 149 -> 139,
-  // down 148 -> 135, lm_head 428 -> 409); FFMI_PREFILL_PLAN=0 keeps the model
-  static const bool prefill_plan = !getenv("FFMI_PREFILL_PLAN") || atoi(getenv("FFMI_PREFILL_PLAN")) != 0;
-  if (prefill_plan && p.mblocks >= 4) {
-    p.NTW = 8;
-    p.S = K >= 8192 && KT >= 2 ? 2 : 1;
-    // 4-row-tile waves run one workgroup per CU: only where the grid still
-    // covers the CUs (T = 1024: o_proj 128 workgroups -> 3-tile waves, 56 vs
-    // 70 us; gate/up, down (2 slices), qkv, lm_head keep 4: 267 vs 280 us,
-    // 131 vs 142 us, equal)
-    if (p.MTW == 4 && (long)((ntiles + 7) / 8) * p.S * p.mblocks < 256) {
-      p.MTW = 3;
-      p.mblocks = (mtiles + 11) / 12;
-    }
-  }
-  // diagnostics: FFMI_GEMM_PLAN="NTW,S" forces the tile width and split of
-  // every M-split launch; "N:K:NTW,S;..." only of the listed shapes (A/B
-  // runs and tests; read per call)
-  const char *force = getenv("FFMI_GEMM_PLAN");
-  if (force) {
-    const char *q = force;
-    while (q && *q) {
-      int a = 0, b = 0, c = 0, d = 0, ntw = 0, S = 0;
-      const int n = sscanf(q, "%d:%d:%d,%d", &a, &b, &c, &d);
-      if (n == 4 && a == N && b == K) ntw = c, S = d;
-      else if (n != 4 && sscanf(q, "%d,%d", &a, &b) == 2) ntw = a, S = b;
-      if ((ntw == 2 || ntw == 4 || ntw == 6 || ntw == 8 || ntw == 12 || ntw == 16) && S >= 1 &&
-          S <= std::min(KT, 8)) {
-        p.NTW = ntw, p.S = S;
-        break;
+// ---------------------------------------------------------------------------
+// Launch: validate -> plan_gemm (gemm_plan.h) -> instantiate and issue what
+// the plan says.  Run-time values become template arguments through these two
+// helpers and the instantiation lists of gemm_plan.h only: a value outside its
+// list launches nothing and the caller reports hipErrorInvalidValue.
+// ---------------------------------------------------------------------------
+// f(std::integral_constant<size_t, index of v in list>); false: v is not listed
+template <class V, size_t N, class F, size_t... I>
+static bool dispatch_impl(const V (&list)[N], const V &v, F &&f, std::index_sequence<I...>) {
+  return ((list[I] == v && (f(std::integral_constant<size_t, I>{}), true)) || ...);
+}
+template <class V, size_t N, class F>
+static bool dispatch(const V (&list)[N], const V &v, F &&f) {
+  return dispatch_impl(list, v, f, std::make_index_sequence<N>{});
+}
+// f(std::true_type or std::false_type for each of the bools)
+template <class F>
+static void dispatch_bools(F &&f) { f(); }
+template <class F, class... B>
+static void dispatch_bools(F &&f, bool b, B... rest) {
+  if (b) dispatch_bools([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+  else dispatch_bools([&](auto... c) { f(std::false_type{}, c...); }, rest...);
+}
+
+static bool launch_reduce(int epi, int MAXS, const float *part, uint16_t *Y, int T, int N,
+                          int ntiles, int S, int yp, hipStream_t s) {
+  const long total = (long)T * ((N + 3) / 4);
+  const unsigned blocks = (unsigned)((total + 255) / 256);
+  bool done = false;
+  dispatch(kReduceMaxS, MAXS, [&](auto mi) {
+    dispatch_bools([&](auto e) {
+      constexpr int MS = kReduceMaxS[decltype(mi)::value], EPI = decltype(e)::value;
+      if constexpr (reduce_instantiated(EPI, MS)) {
+        hipLaunchKernelGGL((gemm_reduce_kernel<EPI, MS>), dim3(blocks), dim3(256), 0, s, part, Y,
+                           T, N, ntiles, S, yp);
+        done = true;
       }
-      q = strchr(q, ';');
-      if (q) ++q;
-    }
-  }
-  if (p.MTW == 4 && p.NTW > 8) p.NTW = 8;
-  p.nblk = (ntiles + p.NTW - 1) / p.NTW;
-  return p;
-}
-
-// Launch form of an unfused GEMM (epi without the layout flags): what
-// launch_gemm dispatches on and gemm_debug_plan reports.
-enum { GEMM_SKINNY = 0, GEMM_WAVE = 1, GEMM_MID = 2, GEMM_TILE = 3 };
-static int gemm_path(int T, int N, int K, int epi, bool xp, bool deferrable) {
-  const int mtiles = (T + 15) / 16;
-  // prefill blocks: the compute-bound 256 x 256 tile form where its grid
-  // covers the CUs (FFMI_TILE_GEMM: 0 never, 2 whenever the shape allows --
-  // A/B runs and tests; read per call)
-  if (mtiles >= 32 && xp) {
-    const char *e = getenv("FFMI_TILE_GEMM");
-    const int mode = e ? atoi(e) : 1;
-    const int ntiles = (N + 15) / 16 * (epi ? 2 : 1);
-    const int nbn = (ntiles + 15) / 16, nbm = (mtiles + 15) / 16;
-    // one 256 x 256 tile per CU and round: worth it where the rounds are
-    // well filled (T = 1024: qkv 192 tiles 168 -> 140 us, lm_head 500 tiles
-    // 396 -> 314, gate/up 344 tiles 274 -> 268; T = 577: gate/up's 258 tiles
-    // = one round + 2, 188 -> 221, stays M-split)
-    const int nwg = nbn * nbm, rounds = (nwg + 255) / 256;
-    if (mode == 2 || (mode == 1 && nwg >= 160 && nwg * 10 >= rounds * 256 * 6)) return GEMM_TILE;
-  }
-  if (mtiles > 4) return GEMM_MID;
-  return wave_form(N, K / 32, epi, skinny_split(T, N, K, epi, deferrable)) ? GEMM_WAVE : GEMM_SKINNY;
-}
-
-size_t gemm_workspace_bytes(int T, int N, int K, int epilogue) {
-  epilogue &= ~(FFMI_X_PACKED | FFMI_Y_PACKED | FFMI_W_STREAM);
-  const int mtiles = (T + 15) / 16;
-  if (mtiles <= 4) {
-    const int S = skinny_split(T, N, K, epilogue, true);
-    return S > 1 ? (size_t)S * T * ((N + 15) / 16) * 16 * sizeof(float) : 0;
-  }
-  const int ntiles = (N + 15) / 16 * (epilogue ? 2 : 1);
-  const int S = std::max(mid_plan(T, N, K, epilogue, false).S,
-                         epilogue ? 1 : mid_plan(T, N, K, epilogue, true).S);
-  return S > 1 ? (size_t)S * T * ntiles * 16 * sizeof(float) : 0;
-}
-
-template <int MTW, int NTW, int PF>
-static hipError_t run_mid(const uint16_t *X, const uint16_t *Wp, uint16_t *Y, float *ws,
-                          size_t ws_bytes, int T, int N, int K, int epi, hipStream_t s,
-                          bool xpacked, int yp, int S, Partials *defer, bool nt, int wpitch) {
-  const int KT = K / 32;
-  const int ntiles = (N + 15) / 16 * (epi ? 2 : 1);
-  const size_t wts = w_tile_stride(KT), wks = w_k_stride(wpitch ? wpitch : ntiles);
-  const int mtiles = (T + 15) / 16;
-  const int mblocks = (mtiles + 4 * MTW - 1) / (4 * MTW);
-  const int nblk = (ntiles + NTW - 1) / NTW;
-  const size_t need = (size_t)S * T * ntiles * 16 * sizeof(float);
-  if (S > 1 && (!ws || ws_bytes < need)) S = 1;  // no workspace: un-split (slower)
-  dim3 grid(nblk, S, mblocks);
-  // split-K launches: the workgroups of a k-slice renumbered onto the same
-  // XCDs, so that an XCD's L2 fetches only its slices' X columns
-  // (mid_xcd_map).  From 4 slices on: with 2 (qkv at T = 168) every XCD still
-  // needs half of X and the launch measured no faster.
-  // FFMI_MID_XCD: 0 blockIdx numbering, 1 the default, 2 every split launch
-  // (A/B runs and tests; read per call)
-  const char *xe = getenv("FFMI_MID_XCD");
-  const int xmode = xe ? atoi(xe) : 1;
-  const int xmap = xmode != 0 && S >= (xmode == 2 ? 2 : 4);
-  static const bool stamp = getenv("FFMI_GEMM_STAMP") != nullptr;
-  // unconditional weight loads (ULD) whenever NTW % 4 != 0 (gate/up T = 168:
-  // 55.9 -> 51.2 us, qkv 37.2 -> 34.6 us in scripts/gemm_bench.py);
-  // FFMI_MID_ULD=0 turns them off (A/B runs)
-  static const bool uld = !getenv("FFMI_MID_ULD") || atoi(getenv("FFMI_MID_ULD")) != 0;
-  // non-temporal weight loads only where each weight tile has ONE reader
-  // (mblocks == 1); prefill blocks re-read every tile from L2 / the MALL
-  const bool ntl = nt && mblocks == 1;
-#define FFMI_MID2(E, ST, XPK, U, NL)                                                               \
-  hipLaunchKernelGGL((gemm_mid_kernel<MTW, NTW, PF, E, ST, XPK, U, NL>), grid, dim3(256), 0, s, X, \
-                     Wp, Y, ws, T, N, K, KT, ntiles, S, yp, wts, wks, xmap)
-#define FFMI_MID(E, ST, XPK)                                  \
-  do {                                                        \
-    const bool u_ = uld && NTW % 4;                           \
-    if (ST) FFMI_MID2(E, ST, XPK, false, false);              \
-    else if (u_ && ntl) FFMI_MID2(E, false, XPK, true, true); \
-    else if (u_) FFMI_MID2(E, false, XPK, true, false);       \
-    else if (ntl) FFMI_MID2(E, false, XPK, false, true);      \
-    else FFMI_MID2(E, false, XPK, false, false);              \
-  } while (0)
-  if (stamp && !epi && stamp_buf()) {
-    g_stamp_entries = (long)nblk * S * mblocks * 4;
-    if (xpacked) FFMI_MID(0, true, true);
-    else FFMI_MID(0, true, false);
-  } else if (xpacked) {
-    if (epi) FFMI_MID(1, false, true);
-    else FFMI_MID(0, false, true);
-  } else {
-    if (epi) FFMI_MID(1, false, false);
-    else FFMI_MID(0, false, false);
-  }
-#undef FFMI_MID
-#undef FFMI_MID2
-  if (defer) {
-    defer->S = 0;
-    if (S > 1 && !epi) {  // the consumer combines the slabs
-      defer->p = ws, defer->S = S, defer->NP = ntiles * 16;
-      return hipGetLastError();
-    }
-  }
-  if (S > 1) {
-    const long total = (long)T * ((N + 3) / 4);
-    const unsigned blocks = (unsigned)((total + 255) / 256);
-#define FFMI_RED(E, MS)                                                                    \
-  hipLaunchKernelGGL((gemm_reduce_kernel<E, MS>), dim3(blocks), dim3(256), 0, s, ws, Y, T, N, \
-                     ntiles, S, yp)
-    if (epi) {
-      if (S <= 2) FFMI_RED(1, 2);
-      else if (S <= 4) FFMI_RED(1, 4);
-      else FFMI_RED(1, 8);
-    } else {
-      if (S <= 2) FFMI_RED(0, 2);
-      else if (S <= 4) FFMI_RED(0, 4);
-      else FFMI_RED(0, 8);
-    }
-#undef FFMI_RED
-  }
-  return hipGetLastError();
+    }, epi != 0);
+  });
+  return done;
 }
 
 hipError_t launch_partials_reduce(const Partials &p, uint16_t *Y, int T, int N, hipStream_t s) {
   if (T <= 0 || p.S <= 0) return hipSuccess;
   // (> 8: the per-head o-projection slabs of a small model, OprojArgs)
   if (p.S > 16 || p.NP % 16 || N > p.NP) return hipErrorInvalidValue;
-  const long total = (long)T * ((N + 3) / 4);
-  const unsigned blocks = (unsigned)((total + 255) / 256);
-#define FFMI_PRED(MS)                                                                          \
-  hipLaunchKernelGGL((gemm_reduce_kernel<0, MS>), dim3(blocks), dim3(256), 0, s, p.p, Y, T, N, \
-                     p.NP / 16, p.S, 0)
-  if (p.S <= 2) FFMI_PRED(2);
-  else if (p.S <= 4) FFMI_PRED(4);
-  else if (p.S <= 8) FFMI_PRED(8);
-  else FFMI_PRED(16);
-#undef FFMI_PRED
+  if (!launch_reduce(0, reduce_maxs(p.S), p.p, Y, T, N, p.NP / 16, p.S, 0, s))
+    return hipErrorInvalidValue;
   return hipGetLastError();
 }
 
@@ -1313,82 +962,80 @@ hipError_t launch_gemm(const uint16_t *X, const uint16_t *Wp, uint16_t *Y, float
                        Partials *defer, int wpitch, const FuseArgs *fuse) {
   if (defer) defer->S = 0;
   if (T <= 0) return hipSuccess;
-  const int KT = K / 32;
-  const int mtiles = (T + 15) / 16;
-  const bool xp = (epilogue & FFMI_X_PACKED) != 0;
-  const int yp = (epilogue & FFMI_Y_PACKED) ? 1 : 0;
-  const bool nt = (epilogue & FFMI_W_STREAM) != 0;
-  epilogue &= ~(FFMI_X_PACKED | FFMI_Y_PACKED | FFMI_W_STREAM);
-  if ((xp && K % 32) || (yp && N % 32)) return hipErrorInvalidValue;
-  if (fuse && fuse->kind) {
-    // producer: row-major residual out, plain epilogue; consumer: row-major X
-    // (the residual), K = the norm width; both unsplit, T <= 32
-    if (mtiles > 2 || N % 16 || K % 32) return hipErrorInvalidValue;
-    if (fuse->kind == 1 && (epilogue || yp || !fuse->res_in || !fuse->ss_out))
-      return hipErrorInvalidValue;
-    if (fuse->kind == 2 && (xp || !fuse->ss_in || !fuse->wnorm || fuse->nss <= 0 || fuse->nss > 256))
-      return hipErrorInvalidValue;
-    const int wp = wpitch ? wpitch : (epilogue == FFMI_EPI_SILU_MUL ? 2 : 1) * ((N + 15) / 16);
-#define FFMI_FZ(MTV, FZV) \
-  return dispatch_fused<MTV, 8, FZV>(X, Wp, Y, T, N, K, KT, epilogue, s, xp, yp, nt, wp, *fuse)
-    if (mtiles <= 1) {
-      if (fuse->kind == 1) FFMI_FZ(1, 1);
-      FFMI_FZ(1, 2);
-    }
-    if (fuse->kind == 1) FFMI_FZ(2, 1);
-    FFMI_FZ(2, 2);
-#undef FFMI_FZ
+  const FuseArgs fz = fuse ? *fuse : FuseArgs();
+  if (fz.kind == 1 && (!fz.res_in || !fz.ss_out)) return hipErrorInvalidValue;
+  if (fz.kind == 2 && (!fz.ss_in || !fz.wnorm || fz.nss <= 0 || fz.nss > 256))
+    return hipErrorInvalidValue;
+  const GemmPlan p = plan_gemm(T, N, K, epilogue, defer != nullptr, fz.kind, ws ? ws_bytes : 0);
+  if (!p.valid) return hipErrorInvalidValue;
+
+  const int xp = p.XP ? 1 : 0, yp = (epilogue & FFMI_Y_PACKED) ? 1 : 0;
+  const int KT = p.KT, ntiles = p.ntiles, S = p.S;
+  const size_t wts = w_tile_stride(KT), wks = w_k_stride(wpitch ? wpitch : ntiles);
+  const dim3 grid(p.grid[0], p.grid[1], p.grid[2]), block(p.block);
+  bool done = false;  // the plan's kernel is instantiated and was launched
+  if (p.form == GEMM_SKINNY) {
+    dispatch(kRowTiles, p.MT, [&](auto mi) {
+      dispatch(kSkinnyForms, SkinnyForm{p.NT, p.KW, p.EPI, p.FZ}, [&](auto fi) {
+        dispatch_bools([&](auto pipe, auto ntl) {
+          constexpr int MT = kRowTiles[decltype(mi)::value], U = skinny_unroll(MT);
+          constexpr SkinnyForm f = kSkinnyForms[decltype(fi)::value];
+          if constexpr (MT <= skinny_max_row_tiles(f.FZ)) {
+            if (p.U != U) return;
+            hipLaunchKernelGGL((gemm_skinny_kernel<MT, f.NT, f.KW, U, f.EPI, decltype(pipe)::value,
+                                                   decltype(ntl)::value, f.FZ>),
+                               grid, block, p.lds, s, X, Wp, Y, ws, T, N, K, KT, ntiles, xp, yp,
+                               wts, wks, fz);
+            done = true;
+          }
+        }, p.PIPE, p.NTL);
+      });
+    });
+  } else if (p.form == GEMM_WAVE) {
+    dispatch(kRowTiles, p.MT, [&](auto mi) {
+      dispatch(kWaveForms, WaveForm{p.NT, p.WPG}, [&](auto fi) {
+        dispatch_bools([&](auto ntl) {
+          constexpr int MT = kRowTiles[decltype(mi)::value];
+          constexpr WaveForm f = kWaveForms[decltype(fi)::value];
+          hipLaunchKernelGGL((gemm_wave_kernel<MT, f.NT, kWaveUB, decltype(ntl)::value, f.WPG>),
+                             grid, block, 0, s, X, Wp, Y, T, N, KT, ntiles, xp, yp, wts, wks);
+          done = true;
+        }, p.NTL);
+      });
+    });
+  } else if (p.form == GEMM_MID) {
+    // (the stamp variant only if its buffer can be had; it has ULD = NTL = false)
+    const bool stamp = p.STAMP && stamp_buf();
+    if (stamp) g_stamp_entries = (long)p.nblk * S * p.mblocks * 4;
+    dispatch(kMidShapes, MidShape{p.MTW, p.NTW}, [&](auto si) {
+      dispatch_bools([&](auto e, auto xpk, auto st, auto uld, auto ntl) {
+        constexpr MidShape m = kMidShapes[decltype(si)::value];
+        constexpr int EPI = decltype(e)::value;
+        constexpr bool ST = decltype(st)::value, ULD = decltype(uld)::value, NTL = decltype(ntl)::value;
+        if constexpr (!ST || (!EPI && !ULD && !NTL)) {
+          hipLaunchKernelGGL((gemm_mid_kernel<m.MTW, m.NTW, kMidPF, EPI, ST, decltype(xpk)::value, ULD, NTL>),
+                             grid, block, 0, s, X, Wp, Y, ws, T, N, K, KT, ntiles, S, yp, wts, wks,
+                             p.xmap);
+          done = true;
+        }
+      }, p.EPI != 0, p.XP, stamp, !stamp && p.ULD, !stamp && p.NTL);
+    });
+  } else if (p.form == GEMM_TILE) {
+    dispatch_bools([&](auto e) {
+      hipLaunchKernelGGL((gemm_tile_kernel<decltype(e)::value, kTileNB>), grid, block, 0, s, X, Wp,
+                         Y, T, N, KT, ntiles, p.mtiles, p.nbm, yp, wts, wks);
+      done = true;
+    }, p.EPI != 0);
   }
-  const int path = gemm_path(T, N, K, epilogue, xp, defer != nullptr);
-  if (path == GEMM_TILE) {
-    const int ntiles = (N + 15) / 16 * (epilogue ? 2 : 1);
-    const int nbn = (ntiles + 15) / 16, nbm = (mtiles + 15) / 16;
-    const size_t wts = w_tile_stride(KT), wks = w_k_stride(wpitch ? wpitch : ntiles);
-    if (epilogue)
-      hipLaunchKernelGGL((gemm_tile_kernel<1, 4>), dim3(nbn * nbm), dim3(512), 0, s, X, Wp, Y, T,
-                         N, KT, ntiles, mtiles, nbm, yp, wts, wks);
-    else
-      hipLaunchKernelGGL((gemm_tile_kernel<0, 4>), dim3(nbn * nbm), dim3(512), 0, s, X, Wp, Y, T,
-                         N, KT, ntiles, mtiles, nbm, yp, wts, wks);
-    return hipGetLastError();
+  if (!done) return hipErrorInvalidValue;
+  if (S > 1 && p.defer) {  // the consumer combines the slabs
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) defer->p = ws, defer->S = S, defer->NP = ntiles * 16;
+    return e;
   }
-  if (path == GEMM_MID) {
-    const MidPlan p = mid_plan(T, N, K, epilogue, defer != nullptr && !epilogue);
-#define FFMI_RUN(M, NW) \
-  return run_mid<M, NW, 4>(X, Wp, Y, ws, ws_bytes, T, N, K, epilogue, s, xp, yp, p.S, defer, nt, \
-                           wpitch)
-    if (p.MTW == 4) {
-      if (p.NTW == 2) FFMI_RUN(4, 2);
-      if (p.NTW == 4) FFMI_RUN(4, 4);
-      if (p.NTW == 6) FFMI_RUN(4, 6);
-      FFMI_RUN(4, 8);  // (12 / 16 tiles: 4 x 16 accumulators exceed the register budget)
-    }
-    if (p.MTW == 3) {
-      if (p.NTW == 2) FFMI_RUN(3, 2);
-      if (p.NTW == 4) FFMI_RUN(3, 4);
-      if (p.NTW == 16) FFMI_RUN(3, 16);
-      if (p.NTW == 12) FFMI_RUN(3, 12);
-      if (p.NTW == 6) FFMI_RUN(3, 6);
-      FFMI_RUN(3, 8);
-    }
-    if (p.NTW == 2) FFMI_RUN(2, 2);
-    if (p.NTW == 4) FFMI_RUN(2, 4);
-    if (p.NTW == 16) FFMI_RUN(2, 16);
-    if (p.NTW == 12) FFMI_RUN(2, 12);
-    if (p.NTW == 6) FFMI_RUN(2, 6);
-    FFMI_RUN(2, 8);
-#undef FFMI_RUN
-  }
-  const int xi = xp ? 1 : 0;
-  int S = skinny_split(T, N, K, epilogue, defer != nullptr);
-  const size_t need = (size_t)S * T * ((N + 15) / 16) * 16 * sizeof(float);
-  if (S > 1 && (!ws || ws_bytes < need)) S = 1;
-  hipError_t e;
-  if (mtiles <= 1) e = dispatch_nt<1, 8>(X, Wp, Y, ws, T, N, K, KT, epilogue, S, s, xi, yp, nt, wpitch);
-  else if (mtiles <= 2) e = dispatch_nt<2, 8>(X, Wp, Y, ws, T, N, K, KT, epilogue, S, s, xi, yp, nt, wpitch);
-  else e = dispatch_nt<4, 4>(X, Wp, Y, ws, T, N, K, KT, epilogue, S, s, xi, yp, nt, wpitch);
-  if (S > 1 && e == hipSuccess) defer->p = ws, defer->S = S, defer->NP = (N + 15) / 16 * 16;
-  return e;
+  if (S > 1 && !launch_reduce(p.EPI, p.MAXS, ws, Y, T, N, ntiles, S, yp, s))
+    return hipErrorInvalidValue;
+  return hipGetLastError();
 }
 
 // Packed activation tiles: Xp[mt][kt][lane][8] = X[mt*16 + (lane&15)][kt*32 + 8(lane>>4) + e]
@@ -1410,21 +1057,6 @@ hipError_t launch_pack_act(const uint16_t *X, uint16_t *Xp, int T, int K, hipStr
   hipLaunchKernelGGL(pack_act_kernel, dim3(K / 32, (T + 15) / 16), dim3(64), 0, s, X, Xp, T, K,
                      K / 32);
   return hipGetLastError();
-}
-
-// diagnostics: {path, MTW, NTW, S, mblocks, nblk} of the launch launch_gemm
-// makes for these arguments without a deferred consumer (ffmi_linear); the
-// last five describe the M-split grid and are 0, 0, 1, 0, 0 on the other
-// paths.  Host only: no launch, no device.
-void gemm_debug_plan(int T, int N, int K, int epilogue, int *plan) {
-  const bool xp = (epilogue & FFMI_X_PACKED) != 0;
-  epilogue &= ~(FFMI_X_PACKED | FFMI_Y_PACKED | FFMI_W_STREAM);
-  plan[0] = gemm_path(T, N, K, epilogue, xp, false);
-  plan[1] = plan[2] = plan[4] = plan[5] = 0;
-  plan[3] = 1;
-  if (plan[0] != GEMM_MID) return;
-  const MidPlan p = mid_plan(T, N, K, epilogue, false);
-  plan[1] = p.MTW, plan[2] = p.NTW, plan[3] = p.S, plan[4] = p.mblocks, plan[5] = p.nblk;
 }
 
 // diagnostics: stamps of the last FFMI_GEMM_STAMP launch (8 int64 per wave)

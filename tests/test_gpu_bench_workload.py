@@ -1,7 +1,7 @@
 """Parity at the bench's own workload: bench.py's LLaMA-7B (32 layers, its
 seed) and LLaMA-68M SSM, its 8 prompts (BOS + 127 splitmix64 ids), its
 max_tokens_per_batch 1024 -- so the prefill is ONE T = 1024 step, which takes
-the M-split GEMM's fixed prefill plan (gemm.hip mid_plan, >= 4 row blocks)
+the M-split GEMM's fixed prefill plan (gemm_plan.cpp mid_plan, >= 4 row blocks)
 and the two-launch attention path -- and 64 decoded tokens per request
 (decode reaches context 192), incremental decoding and SpecInfer (widths
 (1,1,3), 8 SSM steps per verify, T = 168 verify steps).  Configs B and C of

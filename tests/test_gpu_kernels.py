@@ -1127,8 +1127,8 @@ def test_linear_weight_stream_hint(T, epi, K):
     Y0, Y1 = Buf.empty((T, N), np.float16), Buf.empty((T, N), np.float16)
     F.check(L.ffmi_linear(Xb.ptr, Wp.ptr, Y0.ptr, T, N, K, epi, None))
     F.check(L.ffmi_linear(Xb.ptr, Wp.ptr, Y1.ptr, T, N, K, epi | F.W_STREAM, None))
-    # the 4-wave rule under the hint is a fixed 64 k-steps per slice (gemm.hip
-    # dispatch_nt), independent of T
+    # the 4-wave rule under the hint is a fixed 64 k-steps per slice (gemm_plan.cpp
+    # skinny_tiles), independent of T
     if T > 64 or epi or K // 32 < 64:
         assert np.array_equal(Y0.get().view(np.uint16), Y1.get().view(np.uint16))
     else:

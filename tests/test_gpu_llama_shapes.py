@@ -11,7 +11,7 @@ Shapes (SURVEY.md §8 constants):
   4000x8192;
 - T = 8 (decode batch, skinny kernel), T = 168 (8 requests x 21-token
   verify trees, M-split kernel), T = 577 (the first T with >= 4 row blocks:
-  the fixed prefill plan of gemm.hip mid_plan) and T = 1024 (bench.py's
+  the fixed prefill plan of gemm_plan.cpp mid_plan) and T = 1024 (bench.py's
   prefill step: 8 prompts x 128 tokens, max_tokens_per_batch 1024).
 Tolerance as test_gpu_kernels.close16: <= 2 fp16 ulp (or 1e-4 * max |ref|)
 everywhere and >= 99% of elements bit-identical (only the fp32 summation
