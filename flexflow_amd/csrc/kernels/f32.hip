@@ -20,6 +20,7 @@
 #include <algorithm>
 
 #include "../ffmi_internal.h"
+#include "expf_ref.h"
 
 namespace ffmi {
 
@@ -404,6 +405,12 @@ hipError_t launch_attention_f32(const char *blob, int T, const float *qbuf, cons
 // (float)sum (sum in fp64); k rounds of a block arg-max under the order
 // (p desc, index asc), each round taking the first element after the
 // previous pick in that order (arg_topk.cu:208-330 ties: lower index first).
+// The terms and the probabilities take expf_ref (the host libm's expf bit for
+// bit), not the device library's expf: that one is an ulp off the host's on
+// some inputs near 0, where every term of a flat row lies, and the ulp
+// separates or merges two probabilities whose tie the index rule decides --
+// other ids than the oracle's on up to 55 of 64 flat rows
+// (test_arg_topk_f32_flat_rows).
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(1024) void f32_softmax_topk_kernel(const float *__restrict__ logits,
                                                                int V, int k,
@@ -424,7 +431,7 @@ __global__ __launch_bounds__(1024) void f32_softmax_topk_kernel(const float *__r
   mx = shf[0];
   for (int w = 1; w < nw; ++w) mx = fmaxf(mx, shf[w]);
   double sum = 0.0;
-  for (int i = tid; i < V; i += blockDim.x) sum += (double)expf(__fsub_rn(z[i], mx));
+  for (int i = tid; i < V; i += blockDim.x) sum += (double)expf_ref(__fsub_rn(z[i], mx));
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
   if ((tid & 63) == 0) shd[tid >> 6] = sum;
@@ -438,7 +445,7 @@ __global__ __launch_bounds__(1024) void f32_softmax_topk_kernel(const float *__r
     float bp = -1.f;
     int bi = V;
     for (int i = tid; i < V; i += blockDim.x) {
-      const float p = __fdiv_rn(expf(__fsub_rn(z[i], mx)), s);
+      const float p = __fdiv_rn(expf_ref(__fsub_rn(z[i], mx)), s);
       const bool after = p < pprev || (p == pprev && i > iprev);
       if (after && (p > bp || (p == bp && i < bi))) bp = p, bi = i;
     }

@@ -1,4 +1,4 @@
-// Exhaustive check of the expf_ref restatement (kernels/norm.hip) against
+// Exhaustive check of the expf_ref restatement (kernels/expf_ref.h) against
 // the host libm expf over every float in [-104, 0]: gcc -O2
 // -ffp-contract=off expf_ref_check.c -lm && ./a.out  (glibc 2.35: 1 of 1.1e9
 // differs, at x = -63.1).  FIX=i D=d perturbs table entry i (diagnostics).

@@ -70,6 +70,21 @@ def test_invalid_arguments_return_status_not_abort():
     assert L.ffmi_arg_topk_ws(None, 4, 32000, 1, None, None, None, 0, None) == 1
 
 
+def test_full_precision_attn_handle_over_the_lds_bound():
+    """An fp32 attention handle stages one score per cache slot in LDS:
+    (head_dim + 256 + slots) * 4 <= 64 KiB.  32 slots over that bound (d 128:
+    16032, d 32: 16128) is refused as unsupported before any HIP call, so no
+    device is needed."""
+    L = F.lib()
+    h = ctypes.c_void_p()
+    for d, slots in ((128, 16000), (32, 16096)):
+        assert (d + 256 + slots) * 4 == 64 * 1024
+        cfg = F.AttnCfg(F.ATTN_INC, 1, d, 1, slots, 32, 16, 0.1, 10000.0, 0, 0, 1.0, 1.0, 4.0,
+                        8192, 1)
+        assert L.ffmi_attn_create(ctypes.byref(cfg), ctypes.byref(h)) == 5
+        assert b"full precision" in L.ffmi_last_error()
+
+
 def test_full_precision_model_opts_and_no_device():
     """ffmi_model_opts.full_precision (the reference's --use-full-precision)
     routes creation to the fp32 model, which fails with NO_DEVICE here (no

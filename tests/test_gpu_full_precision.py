@@ -88,6 +88,99 @@ def test_linear_f32_random_shapes(seed):
     assert np.array_equal(y1.view(np.uint32), by.get().view(np.uint32))
 
 
+@pytest.mark.parametrize("N,K", [(48, 32), (272, 1376), (1000, 3072)])
+def test_linear_f32_rows_independent_of_T(N, K):
+    """A row of ffmi_linear_f32 is bit-identical whatever T it is computed in:
+    the four default forms (T <= 16, <= 32, <= 64, > 64) all split k over the
+    workgroup's 4 waves at the same k-blocks and sum the ranges in the same
+    order, so the first T rows of one X, T on both sides of every form's
+    threshold, must equal the same rows of the T = 200 result.  The fp32
+    "SpecInfer == incremental decoding" bar rests on this (a verify row at
+    T = 168 against a decode row at T = 8)."""
+    rng = np.random.default_rng(4100 + OFF + N + K)
+    X = rng.uniform(-1, 1, (200, K)).astype(np.float32)
+    W = rng.uniform(-1, 1, (N, K)).astype(np.float32)
+    bx, bw = Buf(X), Buf(W)
+    L = F.lib()
+
+    def rows(T):
+        by = Buf.empty((T, N), np.float32)
+        assert L.ffmi_linear_f32(bx.ptr, bw.ptr, by.ptr, T, N, K, None) == 0
+        return by.get().view(np.uint32)
+
+    full = rows(200)
+    differing = {}
+    for T in (1, 5, 16, 17, 32, 33, 64, 65, 128, 200):
+        n = int((rows(T) != full[:T]).any(axis=1).sum())
+        if n:
+            differing[T] = n
+    report("linear_f32_rows_independent_of_T", N=N, K=K, rows_differing_by_T=differing)
+    assert not differing, differing
+
+
+# the T > 64 shapes of test_linear_f32_against_fp64
+TILE_CASES = [(168, 1536, 4096), (577, 96, 1376), (1024, 512, 4096)]
+
+
+def _tile_case_operands(T, N, K):
+    rng = np.random.default_rng(T * 7 + N + K)
+    return (rng.uniform(-1, 1, (T, K)).astype(np.float32),
+            rng.uniform(-1, 1, (N, K)).astype(np.float32))
+
+
+def _linear_f32_outputs(env, conn):
+    try:
+        os.environ.update(env)
+        L = F.lib()
+        out = []
+        for T, N, K in TILE_CASES:
+            X, W = _tile_case_operands(T, N, K)
+            bx, bw, by = Buf(X), Buf(W), Buf.empty((T, N), np.float32)
+            F.check(L.ffmi_linear_f32(bx.ptr, bw.ptr, by.ptr, T, N, K, None))
+            out.append(by.get())
+        conn.send(("ok", out))
+    except BaseException as e:  # noqa: BLE001 -- reported to the parent
+        conn.send(("err", repr(e)))
+    finally:
+        conn.close()
+
+
+def test_linear_f32_tile_form_against_fp64():
+    """FFMI_F32_GEMM_TILE=1 (the 2 x 2-wave, 32 x 32-per-wave A/B form of the
+    T > 64 launch, one k chain per wave) under test_linear_f32_against_fp64's
+    bound.  The switch is read once per process, so the form runs in a fresh
+    `spawn` process; its sums are ordered differently from the default form's,
+    so the outputs must also differ from this process's somewhere (the switch
+    took effect)."""
+    import multiprocessing as mp
+    ctx = mp.get_context("spawn")
+    a, b = ctx.Pipe()
+    p = ctx.Process(target=_linear_f32_outputs, args=({"FFMI_F32_GEMM_TILE": "1"}, b))
+    p.start()
+    try:
+        assert a.poll(180), "tile-form process did not answer"
+        st, res = a.recv()
+    finally:
+        p.join(60)
+        if p.is_alive():
+            p.kill()
+    assert st == "ok", res
+    L = F.lib()
+    worst, same = 0.0, True
+    for (T, N, K), y in zip(TILE_CASES, res):
+        X, W = _tile_case_operands(T, N, K)
+        ref = X.astype(np.float64) @ W.astype(np.float64).T
+        mag = np.abs(X).astype(np.float64) @ np.abs(W).astype(np.float64).T
+        err = np.abs(y - ref)
+        worst = max(worst, float((err / mag).max()))
+        assert np.all(err <= 2e-6 * mag + 1e-30), (T, N, K, float((err / mag).max()))
+        bx, bw, by = Buf(X), Buf(W), Buf.empty((T, N), np.float32)
+        assert L.ffmi_linear_f32(bx.ptr, bw.ptr, by.ptr, T, N, K, None) == 0
+        same = same and np.array_equal(by.get().view(np.uint32), y.view(np.uint32))
+    report("linear_f32_tile_form", max_rel_err=worst, identical_to_default=same)
+    assert not same, "FFMI_F32_GEMM_TILE=1 gave the default form's bits: switch not applied?"
+
+
 def ulps32(a, b):
     """distance in fp32 ulps (monotonic int mapping)"""
     def key(x):
@@ -149,6 +242,244 @@ def test_arg_topk_f32_against_oracle(k):
     ids, probs = O.softmax_topk(z, k, fp16=0)
     assert np.array_equal(bi.get(), ids)
     assert ulps32(bp.get(), probs).max() <= 2
+
+
+def _rmsnorm_f32_calls(x1, x2, w, eps=1e-6):
+    """(norm of x1, residual sum, norm of the sum, the same two with
+    residual_out aliasing x1 -- the model's in-place form) from the GPU"""
+    T, H = x1.shape
+    L = F.lib()
+    b1, b2, bw = Buf(x1), Buf(x2), Buf(w)
+    out, res = Buf.empty((T, H), np.float32), Buf.empty((T, H), np.float32)
+    e = ctypes.c_float(eps)
+    assert L.ffmi_rmsnorm_f32(b1.ptr, bw.ptr, out.ptr, T, H, e, None) == 0
+    plain = out.get()
+    assert L.ffmi_residual_rmsnorm_f32(b1.ptr, b2.ptr, bw.ptr, res.ptr, out.ptr, T, H, e,
+                                       None) == 0
+    rsum, rout = res.get(), out.get()
+    out2 = Buf.empty((T, H), np.float32)
+    assert L.ffmi_residual_rmsnorm_f32(b1.ptr, b2.ptr, bw.ptr, b1.ptr, out2.ptr, T, H, e,
+                                       None) == 0
+    return plain, rsum, rout, b1.get(), out2.get()
+
+
+@pytest.mark.parametrize("H", [1, 7, 255, 256, 257, 1000, 4099, 11008])
+def test_rmsnorm_f32_shapes_edges_and_aliasing(H):
+    """ffmi_rmsnorm_f32 / ffmi_residual_rmsnorm_f32 vs the oracle's fp32 mode
+    at H below, at and off the 256 threads (one element or fewer per thread,
+    ragged strides, LLaMA-7B's intermediate width) x T 1 and 300.
+
+    Random-normal rows: <= 1 ulp, >= 99% bit-identical -- the share is taken
+    over the random-normal rows only (all elements of both T, the plain and
+    the residual call) -- and the residual sum bit-exact.  Edge rows (all
+    zeros; rows scaled by 1e-20, where eps dominates the mean square; rows
+    scaled by 1e15) are outside the share: each within 1 ulp, the residual sum
+    bit-exact, and the zero row's output exactly 0 and finite.
+
+    residual_out == x1 (the only form the model uses) must give the bits of
+    the non-aliased call, sum and output."""
+    eps = 1e-6
+    rng = np.random.default_rng(4200 + OFF + H)
+    w = rng.uniform(0.5, 1.5, H).astype(np.float32)
+    exact = []
+    for T in (1, 300):
+        x1 = rng.standard_normal((T, H)).astype(np.float32)
+        x2 = rng.standard_normal((T, H)).astype(np.float32)
+        plain, rsum, rout, asum, aout = _rmsnorm_f32_calls(x1, x2, w, eps)
+        d = ulps32(plain, O.rmsnorm(x1, w, eps, fp16=0))
+        assert d.max() <= 1, (T, int(d.max()))
+        exact.append((d == 0).ravel())
+        rr, ro = O.residual_rmsnorm(x1, x2, w, eps, fp16=0)
+        assert np.array_equal(rsum.view(np.uint32), rr.view(np.uint32)), T
+        d = ulps32(rout, ro)
+        assert d.max() <= 1, (T, int(d.max()))
+        exact.append((d == 0).ravel())
+        assert np.array_equal(asum.view(np.uint32), rsum.view(np.uint32)), T
+        assert np.array_equal(aout.view(np.uint32), rout.view(np.uint32)), T
+    share = float(np.concatenate(exact).mean())
+    # edge rows: zeros | eps-dominated | large
+    e1 = rng.standard_normal((3, H)).astype(np.float32)
+    e2 = rng.standard_normal((3, H)).astype(np.float32)
+    for x in (e1, e2):
+        x[0] = 0.0
+        x[1] *= np.float32(1e-20)
+        x[2] *= np.float32(1e15)
+    plain, rsum, rout, asum, aout = _rmsnorm_f32_calls(e1, e2, w, eps)
+    rr, ro = O.residual_rmsnorm(e1, e2, w, eps, fp16=0)
+    edge_ulp = np.maximum(ulps32(plain, O.rmsnorm(e1, w, eps, fp16=0)), ulps32(rout, ro)).max(axis=1)
+    report("rmsnorm_f32_shapes", H=H, random_rows_exact_share=share,
+           edge_rows_max_ulp=[int(u) for u in edge_ulp])
+    assert np.all(edge_ulp <= 1), edge_ulp
+    assert np.array_equal(rsum.view(np.uint32), rr.view(np.uint32))
+    for o in (plain, rout):
+        assert np.isfinite(o).all()
+        assert np.all(o[0] == 0.0)
+    assert np.array_equal(asum.view(np.uint32), rsum.view(np.uint32))
+    assert np.array_equal(aout.view(np.uint32), rout.view(np.uint32))
+    assert share >= 0.99, share
+
+
+# a: 0, -0, +-1, +-20, +-80 (<= 4 ulp), then +-1e4 (saturated: exact)
+SILU_PLANTED = np.array([0.0, -0.0, 1.0, -1.0, 20.0, -20.0, 80.0, -80.0, 1e4, -1e4], np.float32)
+
+
+def _silu_mul_f32_case(n, rng):
+    """one ffmi_silu_mul_f32 call on random inputs as in
+    test_silu_mul_f32_against_oracle, SILU_PLANTED written over the first and
+    the last 10 values of a where n allows; the planted values are checked
+    here, returns the ulp distances of the random ones"""
+    a = (4 * rng.standard_normal(n)).astype(np.float32)
+    b = rng.standard_normal(n).astype(np.float32)
+    planted = np.zeros(n, bool)
+    if n >= 2 * len(SILU_PLANTED):
+        a[:10], a[-10:] = SILU_PLANTED, SILU_PLANTED
+        planted[:10] = planted[-10:] = True
+    ba, bb, bo = Buf(a), Buf(b), Buf.empty((n,), np.float32)
+    assert F.lib().ffmi_silu_mul_f32(ba.ptr, bb.ptr, bo.ptr, n, None) == 0
+    got, ref = bo.get(), O.silu_mul(a, b, fp16=0)
+    d = ulps32(got, ref)
+    sat = planted & (np.abs(a) == np.float32(1e4))
+    assert np.isfinite(got[planted]).all()
+    assert np.array_equal(got[sat], ref[sat]), (got[sat], ref[sat])  # (-0 == 0)
+    # a = 1e4: sigmoid 1, out = a * b; a = -1e4: sigmoid 0, out = +-0
+    assert np.array_equal(got[sat & (a > 0)], (a * b)[sat & (a > 0)])
+    assert np.all(got[sat & (a < 0)] == 0.0)
+    rest = planted & ~sat
+    assert d[rest].max(initial=0) <= 4, d[rest]
+    return d[~planted]
+
+
+def test_silu_mul_f32_short_lengths():
+    """ffmi_silu_mul_f32 at n 1, 255 and 257 (one thread, a ragged block, one
+    thread of a second block) with planted a = 0, -0, +-1, +-20, +-80 (<= 4
+    ulp) and +-1e4 (saturated sigmoid: out = a * b or +-0, equal to the
+    oracle with -0 counted equal to 0).  Random values: <= 4 ulp; >= 90%
+    bit-identical, taken over the random values of the three lengths
+    together (a share of one value says nothing)."""
+    rng = np.random.default_rng(4400 + OFF)
+    d = np.concatenate([_silu_mul_f32_case(n, rng) for n in (1, 255, 257)])
+    report("silu_mul_f32_short_lengths", max_ulp=int(d.max()), exact_share=float((d == 0).mean()))
+    assert d.max() <= 4 and (d == 0).mean() >= 0.9, (int(d.max()), float((d == 0).mean()))
+
+
+def test_silu_mul_f32_grid_stride():
+    """n = 65536 * 256 + 3: past the launch's 65536-block cap, so the first
+    three threads take a second trip of the grid-stride loop; the planted
+    values sit in the first block and in the second trip.  Bars as
+    test_silu_mul_f32_against_oracle: <= 4 ulp, >= 90% bit-identical."""
+    n = 65536 * 256 + 3
+    d = _silu_mul_f32_case(n, np.random.default_rng(4401 + OFF))
+    report("silu_mul_f32_grid_stride", n=n, max_ulp=int(d.max()),
+           exact_share=float((d == 0).mean()))
+    assert d.max() <= 4 and (d == 0).mean() >= 0.9, (int(d.max()), float((d == 0).mean()))
+
+
+def _topk_f32(z, k):
+    """(GPU ids, GPU probs, oracle ids, oracle probs) of ffmi_arg_topk_f32"""
+    z = np.ascontiguousarray(z, np.float32)
+    T, V = z.shape
+    bz, bi, bp = Buf(z), Buf.empty((T, k), np.int32), Buf.empty((T, k), np.float32)
+    assert F.lib().ffmi_arg_topk_f32(bz.ptr, T, V, k, bi.ptr, bp.ptr, None) == 0
+    ids, probs = O.softmax_topk(z, k, fp16=0)
+    return bi.get(), bp.get(), ids, probs
+
+
+@pytest.mark.parametrize("V", [1, 2, 3, 4, 5, 63, 64, 65, 1023, 1024, 1025, 4097, 32001])
+def test_arg_topk_f32_shape_sweep(V):
+    """ffmi_arg_topk_f32 at V below, at and off the wave (64) and the 1024
+    threads (idle threads, k == V, a ragged second trip), every k <= min(4, V),
+    T 1 and 7, random-normal rows scaled by 3: ids exact, probabilities <= 2
+    ulp against the oracle's fp32 mode"""
+    rng = np.random.default_rng(5200 + OFF + V)
+    worst = 0
+    for T in (1, 7):
+        z = (3 * rng.standard_normal((T, V))).astype(np.float32)
+        for k in range(1, min(4, V) + 1):
+            gi, gp, ids, probs = _topk_f32(z, k)
+            assert np.array_equal(gi, ids), (T, k, gi, ids)
+            u = int(ulps32(gp, probs).max())
+            worst = max(worst, u)
+            assert u <= 2, (T, k, u)
+    report("arg_topk_f32_shape_sweep", V=V, max_prob_ulp=worst)
+
+
+@pytest.mark.parametrize("V", [5, 1000, 32001])
+def test_arg_topk_f32_degenerate_rows(V):
+    """k = 4 on rows whose order the probabilities do not decide: all logits
+    equal (ids 0..3); one logit 200 above the rest at index 0, mid-row and
+    V - 1 (every runner-up has probability exactly 0: the lowest remaining
+    indices); some, not all, entries -inf (half of a row, and all but two);
+    rows offset by +1e4 (fp32 spacing ~1e-3: many tied logits) and -1e4.  Ids
+    exact, probabilities <= 2 ulp against the oracle's fp32 mode."""
+    rng = np.random.default_rng(5300 + OFF + V)
+    k = 4
+    base = (3 * rng.standard_normal((9, V))).astype(np.float32)
+    z = base.copy()
+    z[0] = np.float32(0.37)
+    peaks = [0, V // 2, V - 1]
+    for r, j in zip((1, 2, 3), peaks):
+        z[r, j] = z[r].max() + np.float32(200.0)
+    z[4, rng.permutation(V)[:V // 2]] = -np.inf
+    z[5, rng.permutation(V)[:V - 2]] = -np.inf
+    z[6] += np.float32(1e4)
+    z[7] -= np.float32(1e4)
+    z[8] = np.float32(-1e4)  # all equal again, far from 0
+    gi, gp, ids, probs = _topk_f32(z, k)
+    assert np.array_equal(ids[0], np.arange(k)) and np.array_equal(ids[8], np.arange(k))
+    for r, j in zip((1, 2, 3), peaks):
+        assert ids[r].tolist() == [j] + [i for i in range(k + 1) if i != j][:k - 1]
+        assert np.all(probs[r, 1:] == 0.0)
+    assert np.all(probs[5, 2:] == 0.0) and np.all(probs[5, :2] > 0.0)
+    assert np.array_equal(gi, ids), (gi, ids)
+    u = ulps32(gp, probs)
+    report("arg_topk_f32_degenerate_rows", V=V, max_prob_ulp=int(u.max()))
+    assert u.max() <= 2, u
+
+
+def _flat_rows(c, w, V, seed):
+    u = np.random.default_rng(seed).uniform(-1.0, 0.0, (64, V))
+    return (c + u * w).astype(np.float32)
+
+
+def _sensitive_rows(z, ids, probs):
+    """rows whose oracle top-k holds two distinct logits with the same fp32
+    probability: there the index rule decides between unequal logits, and one
+    ulp of expf changes the ids"""
+    n = 0
+    for t in range(z.shape[0]):
+        zt, pt = z[t, ids[t]], probs[t]
+        n += any(pt[i] == pt[j] and zt[i] != zt[j]
+                 for i in range(len(zt)) for j in range(i + 1, len(zt)))
+    return n
+
+
+# (c, w, V) whose oracle rows must be sensitive on at least a quarter of the rows
+FLAT_SENSITIVE = {(0.7, 1e-5, 1000), (0.7, 1e-3, 32000)}
+
+
+@pytest.mark.parametrize("V", [1000, 32000])
+@pytest.mark.parametrize("w", [1e-5, 1e-3])
+@pytest.mark.parametrize("c", [0.7, 0.05])
+def test_arg_topk_f32_flat_rows(c, w, V):
+    """Flat rows, z = float32(c + u * w) with u uniform in [-1, 0), T = 64,
+    k = 4: every term of the softmax is expf of a value within w of 0, where
+    a device expf one ulp off the host's moves a probability across a tie and
+    reorders the ids (the fp16 top-k's round-5 finding).  Ids exact,
+    probabilities <= 2 ulp against the oracle's fp32 mode.  Guard against a
+    vacuous run: at (0.7, 1e-5, 1000) and (0.7, 1e-3, 32000) at least a
+    quarter of the oracle's own rows must be sensitive (_sensitive_rows; 26
+    and 38 of 64 at the default seed, 64 of 64 at c = 0.05, w = 1e-5)."""
+    z = _flat_rows(c, w, V, 1 + OFF)
+    gi, gp, ids, probs = _topk_f32(z, 4)
+    sens = _sensitive_rows(z, ids, probs)
+    rows_off = int((gi != ids).any(axis=1).sum())
+    u = ulps32(gp, probs)
+    report("arg_topk_f32_flat_rows", c=c, w=w, V=V, sensitive_rows=sens, rows_with_other_ids=rows_off,
+           max_prob_ulp=int(u.max()), probs_exact_share=float((u == 0).mean()))
+    if (c, w, V) in FLAT_SENSITIVE:
+        assert sens >= 16, sens
+    assert rows_off == 0, (rows_off, sens)
+    assert u.max() <= 2, int(u.max())
 
 
 def oracle_greedy(om, prompts, n_new):

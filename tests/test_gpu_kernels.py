@@ -14,7 +14,7 @@ import pytest
 
 import flexflow_amd.ffmi as F
 import oracle_lib as O
-from hip_util import Buf, f16, hip, ulp_diff
+from hip_util import Buf, f16, hip, report, ulp_diff
 
 pytestmark = pytest.mark.gpu
 # FFMI_RANDOM_SCALE: k times the seeds of the random-shape tests (one-off sweeps)
@@ -659,6 +659,7 @@ class AttnCase:
         qkv = rng.standard_normal((T, 3 * self.Hl)).astype(np.float32)
         if not self.fp32:
             qkv = f16(qkv)
+        self.last_qkv = qkv  # the step's inputs, for tests that read the caches back
         # tree_vis is derived by ffmi_batch_upload from masks/tree_bit
         toks = (F.TokenInfo * T)(*[F.TokenInfo(*i, 0) for i in infos])
         work = []
@@ -912,7 +913,8 @@ def test_attention_f32_random_trees_vs_oracle(d, seed, monkeypatch):
     _random_tree_case(d, seed, "default", monkeypatch, fp32=True)
 
 
-def _random_tree_case(d, seed, path, monkeypatch, fp32):
+def _random_tree_case(d, seed, path, monkeypatch, fp32, plen_range=(1, 100), max_seq=200,
+                      prefill_rows=None):
     """Tree verification at random shapes against the oracle: 1-4 requests
     with random prompt lengths (crossing the 32-key chunks and the LDS tail),
     random layer-order trees of 1-64 nodes (the merged multi-SSM bound: mask
@@ -921,20 +923,26 @@ def _random_tree_case(d, seed, path, monkeypatch, fp32):
     random tree -- every query row checked against O.attention_row (the
     exact-fraction bar over all rows of the test, not per 128-element row);
     through the default launch, the query-split one (the TP >= 2 form) and
-    the KV-update + attention pair."""
+    the KV-update + attention pair.  plen_range / max_seq: other prompt
+    lengths and the handle to hold them; prefill_rows: check that many
+    sampled prefill rows instead of all (long prompts)."""
     if path == "qsplit":
         monkeypatch.setenv("FFMI_ATTN_QSPLIT", "2")
     elif path == "two_launch":
         monkeypatch.setenv("FFMI_ATTN_NO_FUSE", "1")
     rng = np.random.default_rng(1000 + OFF + 10 * d + seed)
     R = int(rng.integers(1, 5))
-    c = AttnCase(F.ATTN_TREE, d=d, max_requests=4, max_seq=200, tree=64, max_tokens=512,
-                 fp32=fp32)
-    plen = {r: int(rng.integers(1, 100)) for r in range(R)}
+    c = AttnCase(F.ATTN_TREE, d=d, max_requests=4, max_seq=max_seq, tree=64,
+                 max_tokens=max(512, 4 * plen_range[1]), fp32=fp32)
+    plen = {r: int(rng.integers(*plen_range)) for r in range(R)}
     infos = [(3, p, r, p, p + 1, 0, 0, 0) for r in range(R) for p in range(plen[r])]
     out, qs = c.run(infos, masks=[[0]] * R, rng=rng)
     got, want = [], []
-    for t, i in enumerate(infos):
+    rows = range(len(infos))
+    if prefill_rows is not None and prefill_rows < len(infos):
+        rows = np.random.default_rng(seed).choice(len(infos), size=prefill_rows, replace=False)
+    for t in rows:
+        i = infos[t]
         got.append(out[t])
         want.append(c.ref_row(qs[t], i[2], range(i[1] + 1)))
     ntcs = dict(plen)
@@ -1045,21 +1053,23 @@ def test_attention_spec_random_beam_trees_vs_oracle(seed):
 
 @pytest.mark.parametrize("fp32", [False, True])
 def test_attention_spec_beam_layers(fp32):
-    rng = np.random.default_rng(7)
-    c = AttnCase(F.ATTN_SPEC, d=64, fp32=fp32)
-    infos = [(3, p, 0, p, p + 1, 0, 0, 0) for p in range(9)]  # prompt (root = token 8)
+    _spec_beam_layers(AttnCase(F.ATTN_SPEC, d=64, fp32=fp32), 8, np.random.default_rng(7))
+
+
+def _spec_beam_layers(c, ntcs, rng):
+    """beam layers over a prompt of ntcs + 1 tokens (root = the last one)"""
+    infos = [(3, p, 0, p, p + 1, 0, 0, 0) for p in range(ntcs + 1)]
     c.run(infos, masks=[[0]], rng=rng)
-    # tree so far: root(idx0 @ slot 8) -> n1 (idx1) -> {n2, n3} (idx 2,3);
+    # tree so far: root(idx0 @ slot ntcs) -> n1 (idx1) -> {n2, n3} (idx 2,3);
     # this step's layer: n4 (child of n2), n5 (child of n3) at tree idx 4,5
-    ntcs = 8
     parents = [-1, 0, 1, 1, 2, 3]
     m = tree_masks(parents)
     # earlier layers were stored by previous steps: emulate with one step
-    infos = [(5, 9, 0, ntcs + 1, ntcs, ntcs, 2, 1)]
+    infos = [(5, ntcs + 1, 0, ntcs + 1, ntcs, ntcs, 2, 1)]
     c.run(infos, masks=[m], rng=rng)
-    infos = [(5, 10, 0, ntcs + 2 + k, ntcs, ntcs, 4, 2 + k) for k in range(2)]
+    infos = [(5, ntcs + 2, 0, ntcs + 2 + k, ntcs, ntcs, 4, 2 + k) for k in range(2)]
     c.run(infos, masks=[m], rng=rng)
-    infos = [(6, 11, 0, ntcs + 4 + k, ntcs, ntcs, 6, 4 + k) for k in range(2)]
+    infos = [(6, ntcs + 3, 0, ntcs + 4 + k, ntcs, ntcs, 6, 4 + k) for k in range(2)]
     out, qs = c.run(infos, masks=[m], rng=rng)
     for k in range(2):
         j = 4 + k
@@ -1069,6 +1079,202 @@ def test_attention_spec_beam_layers(fp32):
             anc.append(ntcs + a)
             a = parents[a]
         c.check(out[k], c.ref_row(qs[k], 0, list(range(ntcs)) + sorted(anc)))
+
+
+# ------------------------------------------- fp32 attention past 256 keys
+# f32_attention_kernel walks the keys in strides of its 256 threads (scores,
+# exp / sum, and the 256 / d key groups of P.V): beyond 256 visible keys a
+# thread takes a second and later keys.  Bar of every test below:
+# AttnCase.check's fp32 rule, 2e-6 * max(1, max|ref|).  The oracle's fp32 row
+# is within 1.9e-7 of an fp64 softmax.V at 300 - 15999 random-normal keys and
+# the kernel's grouped fp32 summation within 8.1e-8 (numpy emulation), so the
+# bar is ~10x the reference's own error; one dropped key moves an output by
+# ~1e-4 or more.
+def _max_err(got, want):
+    return float(np.abs(np.asarray(got, np.float32) - np.asarray(want, np.float32)).max())
+
+
+@pytest.mark.parametrize("d", [32, 64, 128])
+def test_attention_f32_inc_past_one_pass_of_keys(d):
+    """INC on an fp32 handle, 2 heads: one request prefilled to 1200 keys in
+    steps of at most 512 tokens, a short request interleaved with it (first
+    in the batch in the second step), then a decode token at 1200.  Checked
+    rows: the positions either side of 1, 2 and 4 passes of the 256 threads
+    (254-257, 510-513, 1023, 1024), 1199, 16 more at random, the decode
+    token, and every row of the short request."""
+    rng = np.random.default_rng(4300 + OFF + d)
+    c = AttnCase(F.ATTN_INC, d=d, heads=2, max_requests=2, max_seq=1216, tree=32, max_tokens=512,
+                 fp32=True)
+    fixed = [254, 255, 256, 257, 510, 511, 512, 513, 1023, 1024, 1199]
+    pick = set(fixed) | set(rng.choice(1200, size=16, replace=False).tolist())
+    got, want = [], []
+    steps = [((0, 500), (0, 12)), ((500, 1000), (12, 24)), ((1000, 1200), (24, 31)),
+             ((1200, 1201), (31, 32))]
+    for n, ((a0, a1), (b0, b1)) in enumerate(steps):
+        long_ = [(3, p, 0, p, p + 1, 0, 0, 0) for p in range(a0, a1)]
+        short = [(3, p, 1, p, p + 1, 0, 0, 0) for p in range(b0, b1)]
+        infos = short + long_ if n == 1 else long_ + short
+        assert len(infos) <= 512
+        out, qs = c.run(infos, rng=rng)
+        for t, i in enumerate(infos):
+            if i[2] == 1 or i[1] in pick or i[1] == 1200:
+                got.append(out[t])
+                want.append(c.ref_row(qs[t], i[2], range(i[1] + 1)))
+    assert len(got) >= len(fixed) + 1 + 32
+    report("attention_f32_inc_1200_keys", d=d, rows=len(got),
+           max_abs_err=_max_err(np.stack(got), np.stack(want)))
+    c.check(np.stack(got), np.stack(want))
+
+
+@pytest.mark.parametrize("d", [64, 128])
+@pytest.mark.parametrize("seed", range(2 * RS))
+def test_attention_f32_random_trees_long_prefix(d, seed, monkeypatch):
+    """_random_tree_case on an fp32 handle with prompts of 260-700 tokens, so
+    every tree slot and every commit lies beyond key 256 (64 sampled prefill
+    rows, every tree row of both verify steps)"""
+    _random_tree_case(d, 50 + seed, "default", monkeypatch, fp32=True, plen_range=(260, 701),
+                      max_seq=800, prefill_rows=64)
+
+
+def test_attention_f32_spec_beam_layers_long_prefix():
+    """test_attention_spec_beam_layers on an fp32 handle with a 300-token
+    prefix: the beam layers' tree slots are in the kernel's second pass"""
+    c = AttnCase(F.ATTN_SPEC, d=64, max_seq=352, max_tokens=512, fp32=True)
+    _spec_beam_layers(c, 300, np.random.default_rng(4310 + OFF))
+
+
+@pytest.mark.parametrize("d", [64, 128])
+def test_attention_f32_llama3_rope_scaling(d):
+    """test_attention_llama3_rope_scaling's configuration on an fp32 handle:
+    the handle's host-built llama3 table feeds the fp32 KV update"""
+    rng = np.random.default_rng(200 + d)
+    c = AttnCase(F.ATTN_INC, d=d, theta=500000.0, llama3=(8.0, 1.0, 4.0, 64), fp32=True)
+    lens = {0: 33, 1: 57}
+    infos = [(5, p, r, p, p + 1, 0, 0, 0) for r, n in lens.items() for p in range(n)]
+    out, qs = c.run(infos, rng=rng)
+    want = np.stack([c.ref_row(qs[t], i[2], range(i[1] + 1)) for t, i in enumerate(infos)])
+    report("attention_f32_llama3_rope", d=d, max_abs_err=_max_err(out[:len(infos)], want))
+    c.check(out[:len(infos)], want)
+
+
+def _f32_handle_filled_to_the_last_slot(d, total, name):
+    """An fp32 INC handle of `total` slots (1 head, 1 request) filled
+    cheaply -- fill tokens carry their real pos and store_slot but
+    prefix_len = 1 (ffmi_batch_upload does not relate prefix_len to pos, and
+    the fp32 kernels ignore the work items) -- then three causal queries with
+    the full prefix, the last of which sees the last slot, and one over the
+    first half of the cache that stores nothing."""
+    rng = np.random.default_rng(4320 + OFF + d + total)
+    c = AttnCase(F.ATTN_INC, heads=1, d=d, max_requests=1, max_seq=total - 32, tree=32,
+                 max_tokens=2048, fp32=True)
+    assert c.slots == total
+    fill = total - 3
+    for s in range(0, fill, 2048):
+        c.run([(3, p, 0, p, 1, 0, 0, 0) for p in range(s, min(fill, s + 2048))], rng=rng)
+    mid = total // 2
+    infos = [(3, p, 0, p, p + 1, 0, 0, 0) for p in range(fill, total)] + \
+            [(3, mid, 0, -1, mid, 0, 0, 0)]
+    out, qs = c.run(infos, rng=rng)
+    want = np.stack([c.ref_row(qs[t], 0, range(i[4])) for t, i in enumerate(infos)])
+    report(name, d=d, slots=total, lds_bytes=(d + 256 + total) * 4,
+           max_abs_err=_max_err(out[:len(infos)], want))
+    c.check(out[:len(infos)], want)
+
+
+def test_attention_f32_handle_8192_slots():
+    """an fp32 handle of 8192 slots (33.5 KiB of dynamic LDS, 32 passes of the
+    256 threads), every slot written, queried to the last one"""
+    _f32_handle_filled_to_the_last_slot(128, 8192, "attention_f32_handle_8192_slots")
+
+
+@pytest.mark.parametrize("d,total", [(128, 16000), (32, 16096)])
+def test_attention_f32_handle_at_the_lds_bound(d, total):
+    """The largest fp32 handle ffmi_attn_create accepts: (head_dim + 256 +
+    slots) * 4 == 64 KiB of dynamic LDS exactly, on top of the kernel's 48 B
+    of static LDS.  The launch must be accepted and the row that sees the last
+    slot must be right."""
+    assert (d + 256 + total) * 4 == 64 * 1024
+    _f32_handle_filled_to_the_last_slot(d, total, "attention_f32_handle_at_lds_bound")
+
+
+# ------------------------------------------------ fp32 KV cache, bit-exact
+@pytest.mark.parametrize("d", [64, 128])
+def test_attention_f32_kv_cache_bit_exact(d):
+    """The fp32 K / V caches read back through ffmi_attn_kv_ptrs
+    ([req][head][slot][d]) after every step of a TREE scenario: prefill; a
+    tree step; a step that commits an accepted path, has one commit whose
+    depth equals a slot stored in the same step (commit_overlap: the
+    reference commits, then stores, so the store wins) and one token with
+    store_slot = -1 (staged, not stored); a step that commits that token's
+    staged row.
+
+    Every written K row must equal a*c - b*s | a*s + b*c in numpy float32
+    from O.rope_table (products rounded, then summed: bit for bit the
+    oracle's rope_apply), every written V row the input bits, committed slots
+    the previous step's staged rows, and every slot the step did not write
+    its bits before the step."""
+    rng = np.random.default_rng(4330 + OFF + d)
+    R = 2
+    c = AttnCase(F.ATTN_TREE, d=d, max_requests=R, fp32=True)
+    tab = O.rope_table(c.slots, d, 10000.0).reshape(c.slots, d // 2, 2)
+    h = d // 2
+
+    def read():
+        k, v = ctypes.c_void_p(), ctypes.c_void_p()
+        F.check(L.ffmi_attn_kv_ptrs(c.h, ctypes.byref(k), ctypes.byref(v), None))
+        n = R * c.heads * c.slots * d
+        kc, vc = np.empty(n, np.uint32), np.empty(n, np.uint32)
+        assert hip().hipMemcpy(kc.ctypes.data, k, n * 4, 2) == 0
+        assert hip().hipMemcpy(vc.ctypes.data, v, n * 4, 2) == 0
+        shape = (R, c.heads, c.slots, d)
+        return kc.reshape(shape), vc.reshape(shape)
+
+    state = dict(staged=None, rows=0)
+
+    def step(infos, masks, commits=()):
+        k0, v0 = read()
+        c.run(infos, masks=masks, commits=commits, rng=rng)
+        k1, v1 = read()
+        staged = []
+        for t, i in enumerate(infos):  # this step's rotated k and v, the stated formula
+            x = c.last_qkv[t, c.Hl:2 * c.Hl].reshape(c.heads, d)
+            a, b = x[:, :h], x[:, h:]
+            cs, sn = tab[i[1], :, 0], tab[i[1], :, 1]
+            kr = np.concatenate([a * cs - b * sn, a * sn + b * cs], axis=1)
+            assert kr.dtype == np.float32
+            staged.append((kr, c.last_qkv[t, 2 * c.Hl:].reshape(c.heads, d)))
+        written = {}
+        for src, req, depth in commits:  # commits first, from the previous step's rows
+            written[(req, depth)] = state["staged"][src]
+        for t, i in enumerate(infos):   # then the step's stores
+            if i[3] >= 0:
+                written[(i[2], i[3])] = staged[t]
+        untouched = np.ones((R, c.slots), bool)
+        for (req, slot), (kr, vr) in written.items():
+            untouched[req, slot] = False
+            assert np.array_equal(k1[req, :, slot], kr.view(np.uint32)), ("K", req, slot)
+            assert np.array_equal(v1[req, :, slot], vr.view(np.uint32)), ("V", req, slot)
+        for a1, a0 in ((k1, k0), (v1, v0)):
+            assert np.array_equal(a1.transpose(0, 2, 1, 3)[untouched],
+                                  a0.transpose(0, 2, 1, 3)[untouched])
+        state["staged"] = staged
+        state["rows"] += len(written)
+
+    step([(3, p, 1, p, p + 1, 0, 0, 0) for p in range(12)], [[0]] * 2)
+    parents = [-1, 0, 1, 2, 2, 3, 4]  # root a b c1 c2 d1 d2
+    depth = [12, 13, 14, 15, 15, 16, 16]
+    step([(4, depth[j], 1, 12 + j, 12, 12, 7, j) for j in range(7)], [[0], tree_masks(parents)])
+    # commit root, a, b, c2 to depths 12..15 and d2 to depth 16 -- the slot the
+    # new tree's root stores in this step; the new tree's last node stores nothing
+    commits = [(0, 1, 12), (1, 1, 13), (2, 1, 14), (4, 1, 15), (6, 1, 16)]
+    parents = [-1, 0, 0, 1]
+    dep = [16, 17, 17, 18]
+    infos = [(4, dep[j], 1, 16 + j if j < 3 else -1, 16, 16, 4, j) for j in range(4)]
+    step(infos, [[0], tree_masks(parents)], commits)
+    # commit the row that was only staged (token 3), store one more token
+    step([(4, 19, 1, 19, 19, 0, 0, 0)], [[0]] * 2, [(0, 1, 16), (1, 1, 17), (3, 1, 18)])
+    assert state["rows"] == 12 + 7 + (5 + 3 - 1) + (3 + 1)
+    report("attention_f32_kv_cache_bit_exact", d=d, rows_checked=state["rows"])
 
 
 def test_embedding_exact():
