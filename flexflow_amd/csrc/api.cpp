@@ -45,7 +45,8 @@ extern "C" const char *ffmi_status_str(ffmi_status s) {
 // 0.2: ffmi_attn_cfg.full_precision and ffmi_model_opts.full_precision
 // appended (struct sizes changed), the *_f32 entry points added
 // 0.3: ffmi_rm_config.spec_extensions
-extern "C" const char *ffmi_version(void) { return "ffmi 0.3 (gfx950)"; }
+// 0.4: top-p sampling (ffmi_sample_topp, ffmi_sampling_counter, ffmi_model_set_sampling)
+extern "C" const char *ffmi_version(void) { return "ffmi 0.4 (gfx950)"; }
 
 // ---------------------------------------------------------------------------
 // batch metadata
@@ -57,11 +58,13 @@ extern "C" ffmi_status ffmi_batch_create(int max_tokens, int max_requests, ffmi_
   ffmi_batch_dev *b = new ffmi_batch_dev();
   b->max_tokens = max_tokens;
   b->max_requests = max_requests;
-  // header + tokens + work (<= tokens) + commits (<= tokens) + masks
+  // header + tokens + work (<= tokens) + commits (<= tokens) + masks, and
+  // room behind them for one float per token (a sampling model's draws)
   b->cap = align16(sizeof(ffmi::BatchHeader)) + align16((size_t)max_tokens * sizeof(ffmi_token_info)) +
            align16((size_t)max_tokens * sizeof(ffmi::WorkDev)) +
            align16((size_t)max_tokens * sizeof(ffmi_commit_info)) +
-           align16((size_t)max_requests * FFMI_MAX_TREE * sizeof(uint64_t)) + 64;
+           align16((size_t)max_requests * FFMI_MAX_TREE * sizeof(uint64_t)) + 64 +
+           align16((size_t)max_tokens * sizeof(float));
   // fine-grained (uncached on the device) and mapped: the model's first
   // kernel reads the step's blob straight from here (launch_rmsnorm's fetch)
   if (hipHostMalloc((void **)&b->host, b->cap, hipHostMallocCoherent | hipHostMallocMapped) !=
@@ -601,6 +604,33 @@ extern "C" ffmi_status ffmi_arg_topk_ws(const void *logits, int T, int V, int k,
   FFMI_HIP(ffmi::launch_argmax((const uint16_t *)logits, T, V, k, ids, probs,
                                (hipStream_t)stream, workspace, workspace_bytes));
   return FFMI_OK;
+}
+
+extern "C" size_t ffmi_sample_topp_workspace_bytes(int T, int V) {
+  return ffmi::sample_topp_workspace_bytes(T, V);
+}
+
+extern "C" ffmi_status ffmi_sample_topp(const void *logits, int T, int V, float temperature,
+                                        float topp, const float *u, int32_t *ids, float *probs,
+                                        void *workspace, size_t workspace_bytes,
+                                        ffmi_stream stream) {
+  FFMI_CHECK(logits && u && ids && T >= 0 && V >= 1, FFMI_ERR_INVALID);
+  FFMI_CHECK(temperature > 0.f && topp > 0.f && topp <= 1.f, FFMI_ERR_INVALID);  // (NaN: invalid)
+  FFMI_CHECK(T == 0 || (workspace && workspace_bytes >= ffmi::sample_topp_workspace_bytes(T, V)),
+             FFMI_ERR_INVALID);
+  FFMI_HIP(ffmi::launch_sample_topp((const uint16_t *)logits, T, V, temperature, topp, u, ids, probs,
+                                    workspace, workspace_bytes, (hipStream_t)stream));
+  return FFMI_OK;
+}
+
+extern "C" uint32_t ffmi_sampling_counter(uint64_t seed, int64_t guid, int pos) {
+  uint64_t x = seed ^ ((uint64_t)guid * 0x9e3779b97f4a7c15ull) ^
+               ((uint64_t)(int64_t)pos * 0xd1342543de82ef95ull);
+  x += 0x9e3779b97f4a7c15ull;
+  x = (x ^ (x >> 30)) * 0xbf58476d1ce4e5b9ull;
+  x = (x ^ (x >> 27)) * 0x94d049bb133111ebull;
+  x ^= x >> 31;
+  return (uint32_t)(x >> 40);
 }
 
 // Test hooks of the residual RMSNorm folded into the decode GEMMs (the pair

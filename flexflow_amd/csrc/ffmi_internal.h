@@ -244,6 +244,13 @@ hipError_t launch_argmax(const uint16_t *logits, int T, int V, int k, int32_t *i
                          float *probs, hipStream_t s, void *ws = nullptr, size_t ws_bytes = 0,
                          int32_t *ids2 = nullptr);  // (ids2: a second copy of the ids)
 size_t argmax_workspace_bytes(int T);
+// top-p sampling (llama.cc:286-289): z = x / temperature in fp16, the top-k
+// kernels' p on z, the first token of the (p desc, index asc) order whose
+// cumulative p reaches (u[t] * topp) * topp; ws: sample_topp_workspace_bytes
+hipError_t launch_sample_topp(const uint16_t *logits, int T, int V, float temperature, float topp,
+                              const float *u, int32_t *ids, float *probs, void *ws,
+                              size_t ws_bytes, hipStream_t s);
+size_t sample_topp_workspace_bytes(int T, int V);
 // Vocab-sharded tail (norm.hip): phase 0..2 write this rank's exchange
 // record ([P][T][W] floats, W >= max(4, 2k)); phase 3 merges into ids/probs.
 hipError_t launch_vshard(const uint16_t *logits, int T, int Vl, int P, int rank, int k,

@@ -773,6 +773,203 @@ hipError_t launch_argmax(const uint16_t *logits, int T, int V, int k, int32_t *i
 }
 
 // ---------------------------------------------------------------------------
+// Top-p sampling (llama.cc:286-289: scalar_truediv by the temperature ->
+// softmax -> sampling.cu), one workgroup per row, no sort:
+//   z_i = half(x_i / half(temperature))          (element_unary.cu:80-81,136)
+//   p_i = half(expf(z_i - M) / S), the top-k kernels' probability on z
+//   order (p desc, index asc) (the stable radix sort of sampling.cu:122-135),
+//   pick the first token whose cumulative p reaches t = (u * topp) * topp
+//   (sampling.cu:81,99-100 compares prefix / topp >= u * topp), else the last
+//   token of the order (sampling.cu:94).
+// For p >= 0 the fp16 bit pattern is a monotone key and p <= 1 leaves 15361 of
+// them, every p a multiple of 2^-24 and a row's sum below 2: the cumulative
+// sums are exact in 32-bit integers of that unit, in any summation order.
+//  1. z (kept as fp16 in the row's workspace), the row maximum;
+//  2. S = float(double sum of expf_ref terms), as the top-k kernels';
+//  3. every p_i: its key replaces z in the workspace and its integer mass goes
+//     to an LDS histogram over the keys (LDS atomics: a softmax row spreads
+//     over thousands of keys, so few of them collide);
+//  4. a workgroup scan from the top key down finds the key K at which the
+//     cumulative mass reaches ceil(t * 2^24), and from the mass above K the
+//     rank r, in index order, of the pick among the tokens holding K;
+//  5. the tokens holding K are counted per 64 consecutive indices (one wave
+//     ballot each, the counts in the histogram's LDS), a second scan finds the
+//     group of rank r, and the wave that owns the group emits its lane.
+// The workspace element i is only ever touched by thread i % TPB.
+// ---------------------------------------------------------------------------
+constexpr int kSampleKeys = 0x3c00 + 1;  // keys of p in [0, 1]
+constexpr int kSampleTPB = 1024;
+
+__device__ __forceinline__ unsigned p_mass(unsigned key) {  // p / 2^-24, key <= 0x3c00
+  const unsigned e = key >> 10, m = key & 1023u;
+  return e ? (1024u + m) << (e - 1) : m;
+}
+
+// First position q (scan order: ascending, or descending when DESC) at which
+// the running sum of arr[0 .. N) reaches target (>= 1): res = {q, sum before
+// q}, or {-1, .} when the whole array sums to less.  Each thread sums a
+// contiguous run, a wave scan and the waves' totals order the runs, and the
+// one thread whose run crosses the target walks it.  Ends with a barrier.
+template <int TPB, bool DESC>
+__device__ __forceinline__ void block_find(const unsigned *arr, int N, unsigned target,
+                                           unsigned *wsum, int *res) {
+  constexpr int NW = TPB / 64;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int L = (N + TPB - 1) / TPB;
+  const int q0 = min(tid * L, N), q1 = min(q0 + L, N);
+  auto at = [&](int q) -> unsigned { return arr[DESC ? N - 1 - q : q]; };
+  unsigned s = 0;
+  for (int q = q0; q < q1; ++q) s += at(q);
+  unsigned inc = s;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const unsigned t = __shfl_up(inc, o);
+    if (lane >= o) inc += t;
+  }
+  if (lane == 63) wsum[wv] = inc;
+  if (tid == 0) res[0] = -1;
+  __syncthreads();
+  unsigned c = inc - s;
+#pragma unroll
+  for (int q = 0; q < NW; ++q)
+    if (q < wv) c += wsum[q];
+  if (c < target && target - c <= s)
+    for (int q = q0; q < q1; ++q) {
+      const unsigned v = at(q);
+      if (target - c <= v) {
+        res[0] = q;
+        res[1] = (int)c;
+        break;
+      }
+      c += v;
+    }
+  __syncthreads();
+}
+
+// HWEXP (FFMI_SAMPLE_HWEXP=1, A/B runs only: not the rule's p): the hardware
+// exp2 in place of expf_ref, to measure what the exact terms cost
+template <int TPB, bool HWEXP>
+__global__ __launch_bounds__(TPB) void sample_topp_kernel(
+    const uint16_t *__restrict__ logits, int V, float temperature, float topp,
+    const float *__restrict__ u, int32_t *__restrict__ ids, float *__restrict__ probs,
+    uint16_t *__restrict__ pws) {
+  constexpr int NW = TPB / 64;
+  __shared__ unsigned hist[kSampleKeys];
+  __shared__ double sh[NW];
+  __shared__ unsigned wsum[NW];
+  __shared__ int res[2];
+  float *fsh = reinterpret_cast<float *>(sh);
+  unsigned long long *ksh = reinterpret_cast<unsigned long long *>(sh);
+  const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const uint16_t *x = logits + (size_t)row * V;
+  uint16_t *w = pws + (size_t)row * V;
+  auto ex = [](float d) -> float { return HWEXP ? __expf(d) : expf_ref(d); };
+  for (int i = tid; i < kSampleKeys; i += TPB) hist[i] = 0;
+  const float th = h2f_(f2h_(temperature));
+  float mx = -INFINITY;
+  for (int i = tid; i < V; i += TPB) {
+    const uint16_t z = f2h_(__fdiv_rn(h2f_(x[i]), th));
+    w[i] = z;
+    mx = fmaxf(mx, h2f_(z));
+  }
+  mx = __ockl_wfred_max_f32(mx);
+  if (lane == 0) fsh[wv] = mx;
+  __syncthreads();
+  float M = fsh[0];
+#pragma unroll
+  for (int q = 1; q < NW; ++q) M = fmaxf(M, fsh[q]);
+  __syncthreads();
+  double se = 0.0;
+  for (int i = tid; i < V; i += TPB) se += (double)ex(h2f_(w[i]) - M);
+  se = __ockl_wfred_add_f64(se);
+  if (lane == 0) sh[wv] = se;
+  __syncthreads();
+  double sd = 0.0;
+#pragma unroll
+  for (int q = 0; q < NW; ++q) sd += sh[q];
+  const float S = (float)sd;
+  __syncthreads();
+  // the last token of the order (lowest p, then highest index), for a row
+  // whose whole mass stays below t: the largest (~key, index)
+  unsigned long long lastk = 0;
+  for (int i = tid; i < V; i += TPB) {
+    const unsigned key = f2h_(__fdiv_rn(ex(h2f_(w[i]) - M), S));
+    w[i] = (uint16_t)key;
+    // (a NaN row -- an infinite logit -- has keys outside the histogram: no mass)
+    if (key < (unsigned)kSampleKeys && key) atomicAdd(&hist[key], p_mass(key));
+    const unsigned long long lk = ((unsigned long long)(0xffffu - key) << 32) | (unsigned)i;
+    lastk = lk > lastk ? lk : lastk;
+  }
+  lastk = __ockl_wfred_max_u64(lastk);
+  if (lane == 0) ksh[wv] = lastk;
+  // t * 2^24 rounded up: the smallest integer mass that reaches t
+  unsigned target;
+  {
+    const double t = __dmul_rn(__dmul_rn((double)u[row], (double)topp), (double)topp);
+    const double tm = ceil(__dmul_rn(t, 16777216.0));
+    target = tm >= 1.0 ? (tm < 4.0e9 ? (unsigned)tm : 4000000000u) : 1u;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < NW; ++q) lastk = ksh[q] > lastk ? ksh[q] : lastk;
+  block_find<TPB, true>(hist, kSampleKeys, target, wsum, res);
+  const int kq = res[0];
+  if (kq < 0) {  // (uniform: the whole workgroup leaves)
+    if (tid == 0) {
+      const int i = (int)(lastk & 0xffffffffu);
+      ids[row] = i;
+      if (probs) probs[row] = h2f_((uint16_t)(0xffffu - (unsigned)(lastk >> 32)));
+    }
+    return;
+  }
+  const unsigned K = (unsigned)(kSampleKeys - 1 - kq);
+  const unsigned pm = p_mass(K);
+  const unsigned rank = (target - (unsigned)res[1] + pm - 1) / pm - 1;  // 0-based, among K's tokens
+  __syncthreads();  // (every thread has read res; hist becomes the group counts)
+  const int nchunk = (V + TPB - 1) / TPB;
+  for (int j = 0; j < nchunk; ++j) {
+    const int i = j * TPB + tid;
+    const unsigned long long b = __ballot(i < V && w[i] == (uint16_t)K);
+    if (lane == 0) hist[j * NW + wv] = (unsigned)__popcll(b);
+  }
+  __syncthreads();
+  block_find<TPB, false>(hist, nchunk * NW, rank + 1, wsum, res);
+  const int g = res[0];
+  if (g < 0 || g % NW != wv) return;
+  const int i = (g / NW) * TPB + tid;
+  const bool hit = i < V && w[i] == (uint16_t)K;
+  const unsigned long long b = __ballot(hit);
+  const unsigned below = (unsigned)__popcll(b & ((1ull << lane) - 1ull));
+  if (hit && below == rank - (unsigned)res[1]) {
+    ids[row] = i;
+    if (probs) probs[row] = h2f_((uint16_t)K);
+  }
+}
+
+// one 16-bit word per logit; the histogram's LDS, reused for the counts of
+// whole chunks of 64-index groups, bounds the row length
+constexpr int kSampleMaxV = kSampleKeys / (kSampleTPB / 64) * kSampleTPB;
+size_t sample_topp_workspace_bytes(int T, int V) {
+  return T <= 0 || V <= 0 ? 0 : (size_t)T * (size_t)V * sizeof(uint16_t);
+}
+
+hipError_t launch_sample_topp(const uint16_t *logits, int T, int V, float temperature, float topp,
+                              const float *u, int32_t *ids, float *probs, void *ws,
+                              size_t ws_bytes, hipStream_t s) {
+  if (T <= 0) return hipSuccess;
+  if (V < 1 || V > kSampleMaxV || !ws || ws_bytes < sample_topp_workspace_bytes(T, V))
+    return hipErrorInvalidValue;
+  static const bool hwexp = getenv("FFMI_SAMPLE_HWEXP") && atoi(getenv("FFMI_SAMPLE_HWEXP"));
+  if (hwexp)
+    hipLaunchKernelGGL((sample_topp_kernel<kSampleTPB, true>), dim3(T), dim3(kSampleTPB), 0, s, logits,
+                       V, temperature, topp, u, ids, probs, reinterpret_cast<uint16_t *>(ws));
+  else
+    hipLaunchKernelGGL((sample_topp_kernel<kSampleTPB, false>), dim3(T), dim3(kSampleTPB), 0, s, logits,
+                       V, temperature, topp, u, ids, probs, reinterpret_cast<uint16_t *>(ws));
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
 // Vocab-sharded greedy / speculative tail (model.cc:3392-3419 shards lm_head
 // over the vocabulary and Combines; here every rank keeps its [T][V/P] logit
 // shard and three small exchanges of per-row records make the pick global):

@@ -34,6 +34,16 @@ extern "C" ffmi_status ffmi_model_set_debug(ffmi_model *m, int enable) {
   return m->set_debug(enable);
 }
 
+extern "C" ffmi_status ffmi_model_set_sampling(ffmi_model *m, int do_sample, float temperature,
+                                               float topp, uint64_t seed) {
+  if (!m) return FFMI_ERR_INVALID;
+  // GenerationConfig's constructor (inference.h:28-29); NaN takes the default too
+  if (!(temperature > 0.f)) temperature = 0.8f;
+  if (!(topp > 0.f)) topp = 0.6f;
+  FFMI_CHECK(topp <= 1.f, FFMI_ERR_INVALID);
+  return m->set_sampling(do_sample != 0, temperature, topp, seed);
+}
+
 extern "C" long ffmi_model_debug_tensor(ffmi_model *m, int which, int layer, float *out,
                                         long cap) {
   if (!m || !out || cap <= 0) return -1;

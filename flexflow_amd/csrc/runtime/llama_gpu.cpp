@@ -61,6 +61,57 @@ struct LlamaGPU : public ffmi_model {
   // softmax top-k workspace (the split-row form for small steps; zeroed once)
   void *topk_ws = nullptr;
   size_t topk_ws_bytes = 0;
+  // top-p sampling (ffmi_model_set_sampling; llama.cc:286-289) instead of the
+  // greedy tail.  The host draws one uniform per row, u = (ffmi_sampling_
+  // counter(seed, request guid, position of the token produced) + 1) * 2^-24,
+  // and appends them to the step's blob behind its records (step_u_off), so
+  // they ride the step's one upload and a graph replay reads fresh values
+  bool sampling = false;
+  float temperature = 0.8f, topp = 0.6f;
+  uint64_t sampling_seed = 0;
+  uint16_t *sample_ws = nullptr;  // [Tm][V], allocated when sampling is first turned on
+  std::vector<float> step_u;
+  size_t step_u_off = 0;
+  ffmi_status set_sampling(bool on, float temp, float p, uint64_t seed) override {
+    const char *why = mode != FFMI_MODEL_INC
+                          ? "sampling: a BEAM / TREE model decodes greedily (a sampled pick "
+                            "cannot verify a greedy token tree)"
+                          : Vl != c.vocab_size ? "sampling: vocab-sharded lm_head" : nullptr;
+    if (why) {
+      ffmi_set_last_error(why, __FILE__, __LINE__);
+      return FFMI_ERR_UNSUPPORTED;
+    }
+    const size_t Tm = (size_t)((o.max_tokens + 15) & ~15);
+    if (on && !sample_ws) {
+      const ffmi_status st = alloc(&sample_ws, Tm * c.vocab_size);
+      if (st != FFMI_OK) return st;
+    }
+    // (the captured graphs hold the tail's kernel and its scalar arguments)
+    FFMI_HIP(hipStreamSynchronize(stream));
+    clear_graphs();
+    sampling = on;
+    temperature = temp, topp = p, sampling_seed = seed;
+    return FFMI_OK;
+  }
+  // the step's draws, from the batch the scheduler built
+  void draw_step_u(const BatchConfig &bc) {
+    step_u.resize(bc.num_tokens);
+    for (int t = 0; t < bc.num_tokens; ++t) {
+      const auto &ti = bc.tokensInfo[t];
+      const uint32_t ctr = ffmi_sampling_counter(
+          sampling_seed, bc.requestsInfo[ti.request_index].request_guid, ti.abs_depth_in_request + 1);
+      step_u[t] = (float)(ctr + 1u) * (1.0f / 16777216.0f);
+    }
+  }
+  // append them to the staged blob (forward_launch, after batch_stage)
+  ffmi_status stage_step_u(int T, size_t *bytes) {
+    step_u_off = *bytes;
+    const size_t n = ((size_t)T * sizeof(float) + 15) & ~(size_t)15;
+    FFMI_CHECK((int)step_u.size() == T && *bytes + n <= batch->cap, FFMI_ERR_INVALID);
+    memcpy(batch->host + *bytes, step_u.data(), (size_t)T * sizeof(float));
+    *bytes += n;
+    return FFMI_OK;
+  }
   // vocab-sharded lm_head at TP > 1 (model.cc:3392-3419): this rank's Vl rows
   // and the [P][Tm][kXW] exchange records of the sharded softmax / top-k
   int Vl = 0;
@@ -922,6 +973,7 @@ struct LlamaGPU : public ffmi_model {
     ffmi_status st = ffmi::batch_stage(batch, &desc, &bytes);
     if (st != FFMI_OK) return st;
     if (T == 0) return FFMI_OK;
+    if (sampling && (st = stage_step_u(T, &bytes)) != FFMI_OK) return st;
     probs_h = reinterpret_cast<float *>(ids_h + cur_slot * slot_ints() + (size_t)T * k);
     // graphed: small steps, and tree-verify steps of one work item per
     // request (a fixed shape while the batch is full: T = 168 for 8 requests
@@ -1276,7 +1328,13 @@ struct LlamaGPU : public ffmi_model {
     // keeps the device buffer + copy (A/B runs)
     int32_t *ids_o = result_copy ? ids_d : ids_h + cur_slot * slot_ints();
     float *probs_o = reinterpret_cast<float *>(ids_o + (size_t)T * k);
-    if (Vl != V) {
+    if (sampling) {
+      // (set_sampling: INC, unsharded vocabulary; u behind the blob's records)
+      FFMI_CHECK(k == 1 && Vl == V && sample_ws, FFMI_ERR_INVALID);
+      FFMI_HIP(ffmi::launch_sample_topp(
+          logits, T, V, temperature, topp, reinterpret_cast<const float *>(batch->dev + step_u_off),
+          ids_o, probs_o, sample_ws, ffmi::sample_topp_workspace_bytes(T, V), stream));
+    } else if (Vl != V) {
       // sharded softmax / top-k: three record exchanges, then the merge
       TRY(ffmi_vocab_shard_topk(o.comm, logits, T, Vl, k, ids_o, probs_o, xch, s));
     } else {
@@ -1299,6 +1357,7 @@ struct LlamaGPU : public ffmi_model {
     if (mode != FFMI_MODEL_INC) return FFMI_ERR_INVALID;
     FFMI_CHECK(bc.num_tokens <= o.max_tokens, FFMI_ERR_INVALID);
     pack_inc(bc, o.max_requests, slots, &ps);
+    if (sampling) draw_step_u(bc);
     cur_slot = 0;
     ffmi_status st = forward(1);
     if (st != FFMI_OK) return st;

@@ -110,6 +110,18 @@ struct ffmi_model {
     (void)enable;
     return FFMI_ERR_UNSUPPORTED;
   }
+  // top-p sampling instead of the greedy tail (ffmi_model_set_sampling;
+  // arguments already normalised): only the fp16 incremental-decoding model
+  // with an unsharded vocabulary has it
+  virtual ffmi_status set_sampling(bool on, float temperature, float topp, uint64_t seed) {
+    (void)on;
+    (void)temperature;
+    (void)topp;
+    (void)seed;
+    ffmi_set_last_error("sampling: only an fp16 incremental-decoding model samples", __FILE__,
+                        __LINE__);
+    return FFMI_ERR_UNSUPPORTED;
+  }
   virtual long debug_tensor(int which, int layer, float *out, long cap) {
     (void)which;
     (void)layer;

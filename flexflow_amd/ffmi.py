@@ -174,6 +174,10 @@ SIGNATURES = {
     "ffmi_arg_topk_workspace_bytes": (c_size_t, [c_int]),
     "ffmi_arg_topk_ws": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                  c_size_t, c_void_p]),
+    "ffmi_sample_topp_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "ffmi_sample_topp": (c_int, [c_void_p, c_int, c_int, c_float, c_float, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_size_t, c_void_p]),
+    "ffmi_sampling_counter": (ctypes.c_uint32, [c_uint64, c_int64, c_int]),
     "ffmi_fill_weight": (c_int, [c_void_p, c_size_t, ctypes.c_char_p, c_uint64, c_int, c_void_p]),
     "ffmi_model_create": (c_int, [ctypes.POINTER(LlamaConfig), ctypes.POINTER(ModelOpts),
                                   ctypes.POINTER(c_void_p)]),
@@ -181,6 +185,7 @@ SIGNATURES = {
     "ffmi_model_set_profiling": (c_int, [c_void_p, c_int]),
     "ffmi_model_op_stats": (c_int, [c_void_p, ctypes.POINTER(OpStat), c_int]),
     "ffmi_model_set_debug": (c_int, [c_void_p, c_int]),
+    "ffmi_model_set_sampling": (c_int, [c_void_p, c_int, c_float, c_float, c_uint64]),
     "ffmi_model_debug_tensor": (ctypes.c_long, [c_void_p, c_int, c_int, c_void_p, ctypes.c_long]),
     "ffmi_model_debug_width": (ctypes.c_long, [c_void_p, c_int]),
     "ffmi_model_debug_fault": (c_int, [c_void_p, c_int, c_int, c_int]),
@@ -275,6 +280,12 @@ def check(st, what=""):
     if st != FFMI_OK:
         msg = lib().ffmi_last_error().decode(errors="replace")
         raise FFMIError(f"{what}: {STATUS.get(st, st)} [{msg}]")
+
+
+def sampling_counter(seed: int, guid: int, pos: int) -> int:
+    """ffmi_sampling_counter: the 24-bit draw of token `pos` of request `guid`
+    (host only); the uniform is (counter + 1) * 2**-24, in (0, 1]."""
+    return int(lib().ffmi_sampling_counter(seed & (2**64 - 1), guid, pos))
 
 
 def int_array(vals):

@@ -11,6 +11,20 @@ from typing import List, Optional, Union
 from . import ffmi as F
 
 
+@dataclass
+class GenerationConfig:
+    """The reference's GenerationConfig (python/flexflow/serve/serve.py; C++
+    include/flexflow/inference.h:22-33).  do_sample: top-p sampling of every
+    token of an incremental-decoding model instead of the argmax
+    (llama.cc:286-289; include/ffmi.h ffmi_sample_topp, which keeps the
+    reference's threshold u * topp**2).  topk is accepted and unused, as in
+    the reference."""
+    do_sample: bool = False
+    temperature: float = 0.9
+    topp: float = 0.8
+    topk: int = 1
+
+
 class Model:
     """A LLaMA model on one GPU (one TP shard).  mode: "inc" (incremental
     decoding LLM), "tree" (SpecInfer verify LLM) or "beam" (SSM)."""
@@ -20,13 +34,15 @@ class Model:
     def __init__(self, config: dict, mode: str = "inc", *, max_requests=8, max_tokens=128,
                  max_seq_len=512, max_tree_tokens=23, weight_seed=20250117, tp_rank=0,
                  tp_size=1, comm=None, weights_folder: Optional[str] = None,
-                 weight_init: Union[int, str] = 0, full_precision: bool = False):
+                 weight_init: Union[int, str] = 0, full_precision: bool = False,
+                 generation_config: Optional[GenerationConfig] = None, sampling_seed: int = 0):
         """weights_folder: a checkpoint in the reference's per-tensor format
         (see checkpoint.convert_hf_model); None: seeded synthetic weights,
         `weight_init` "uniform" (0, the bench's), "depth_scaled" (1) or
         "token_chain" (2) -- include/ffmi.h ffmi_model_opts.  full_precision:
         the reference's --use-full-precision (every tensor fp32,
-        runtime/llama_f32.cpp); default the fp16 model."""
+        runtime/llama_f32.cpp); default the fp16 model.  generation_config:
+        see set_sampling (None: greedy decoding)."""
         L = F.lib()
         self.config = dict(config)
         self.mode = mode
@@ -39,6 +55,22 @@ class Model:
         F.check(L.ffmi_model_create(ctypes.byref(cfg), ctypes.byref(opts), ctypes.byref(h)),
                 "ffmi_model_create")
         self.handle = h
+        if generation_config is not None:
+            self.set_sampling(generation_config, sampling_seed)
+
+    def set_sampling(self, generation_config: Optional[GenerationConfig], seed: int = 0):
+        """do_sample: every token of this incremental-decoding model is drawn
+        by top-p sampling at the config's temperature and topp, with the
+        uniform of token `pos` of request `guid` (ffmi.sampling_counter(seed,
+        guid, pos) + 1) * 2**-24, pos the token's index in the request's
+        sequence -- the draws depend on the seed, not on the batching.  None
+        or do_sample False: greedy decoding.  FFMIError
+        (unsupported) on a "beam" / "tree" model, a full_precision model and a
+        vocab-sharded lm_head (ffmi_model_set_sampling)."""
+        gc = generation_config or GenerationConfig()
+        F.check(F.lib().ffmi_model_set_sampling(self.handle, int(bool(gc.do_sample)),
+                                                float(gc.temperature), float(gc.topp),
+                                                seed & (2**64 - 1)), "set_sampling")
 
     def set_profiling(self, level: int):
         F.check(F.lib().ffmi_model_set_profiling(self.handle, level), "set_profiling")

@@ -322,6 +322,40 @@ size_t ffmi_arg_topk_workspace_bytes(int T);
 ffmi_status ffmi_arg_topk_ws(const void *logits, int T, int V, int k, int32_t *ids,
                              float *probs, void *workspace, size_t workspace_bytes,
                              ffmi_stream stream);
+/* Top-p sampling, the do_sample tail of the reference's LLaMA graph
+ * (llama.cc:286-289: scalar_truediv -> softmax -> sampling.cu).  Per row,
+ * with R16 = round-to-nearest-even to fp16:
+ *   z_i = R16(float(x_i) / float(R16(temperature)))
+ *   p_i = the probability ffmi_arg_topk defines on z (fp16 softmax)
+ *   order the tokens by p descending, index ascending among equal p, and pick
+ *   the first whose cumulative p reaches t = (double(u) * topp) * topp; if
+ *   none does, the last token of the order.
+ * ids[t] is the pick, probs[t] (may be NULL) its p.  The threshold is the
+ * reference's (sampling.cu:81,99-100 compares prefix / topp >= u * topp, so
+ * topp = 0.8 draws from the top 0.64 of the mass); the cumulative sums are
+ * exact (integer multiples of 2^-24) and compared in fp64.  `u` is device
+ * memory, one uniform in (0, 1] per row; the caller draws it
+ * (ffmi_sampling_counter gives a reproducible one).  One launch,
+ * graph-capturable; ids / probs may be pinned host memory.  `workspace`
+ * holds ffmi_sample_topp_workspace_bytes(T, V) bytes of device memory (any
+ * contents), one per stream in flight.  V <= 983040.
+ * FFMI_ERR_INVALID: T < 0, V < 1, a null logits / u / ids pointer, a missing
+ * or too small workspace, temperature <= 0, topp outside (0, 1]. */
+size_t ffmi_sample_topp_workspace_bytes(int T, int V);
+ffmi_status ffmi_sample_topp(const void *logits, int T, int V, float temperature, float topp,
+                             const float *u, int32_t *ids, float *probs, void *workspace,
+                             size_t workspace_bytes, ffmi_stream stream);
+/* The sampling draw of a request's token (host only, no device): with
+ *   x = seed ^ (uint64(guid) * 0x9e3779b97f4a7c15) ^ (uint64(pos) * 0xd1342543de82ef95)
+ * the top 24 bits of the splitmix64 finaliser
+ *   x += 0x9e3779b97f4a7c15; x = (x ^ x >> 30) * 0xbf58476d1ce4e5b9;
+ *   x = (x ^ x >> 27) * 0x94d049bb133111eb; x ^= x >> 31
+ * u = (counter + 1) * 2^-24 lies in (0, 1].  `pos` is the index of the token
+ * being produced in the request's token sequence (prompt with BOS, then the
+ * generated tokens), so a draw depends on the seed, the request and the
+ * position only -- not on the batch around it, the prefill chunking or graph
+ * replay. */
+uint32_t ffmi_sampling_counter(uint64_t seed, int64_t guid, int pos);
 /* DT_FLOAT twins (--use-full-precision, kernels/f32.hip): RMSNorm /
  * ResidualRMSNorm (sum of squares in fp64, rounded once; fp32 residual add),
  * SigmoidSiluMulti, softmax + arg-top-k on fp32 probabilities (k <= 4, lowest
@@ -453,6 +487,17 @@ int ffmi_model_op_stats(ffmi_model *m, ffmi_op_stat *out, int cap);
 #define FFMI_DBG_DOWN 8
 #define FFMI_DBG_EMBED 9
 ffmi_status ffmi_model_set_debug(ffmi_model *m, int enable);
+/* GenerationConfig(do_sample, temperature, topp) of the reference
+ * (inference.h:22-33, llama.cc:284-295).  do_sample != 0: an incremental-
+ * decoding model picks every token with ffmi_sample_topp instead of the
+ * argmax, u = (ffmi_sampling_counter(seed, request guid, position) + 1) *
+ * 2^-24.  temperature <= 0 becomes 0.8 and topp <= 0 becomes 0.6, as the
+ * reference's constructor; topp > 1 is FFMI_ERR_INVALID.  do_sample == 0
+ * restores the greedy tail.  FFMI_ERR_UNSUPPORTED (message in
+ * ffmi_last_error) for a BEAM or TREE model (a sampled pick cannot verify a
+ * greedy token tree), a full_precision model and a vocab-sharded lm_head. */
+ffmi_status ffmi_model_set_sampling(ffmi_model *m, int do_sample, float temperature, float topp,
+                                    uint64_t seed);
 long ffmi_model_debug_tensor(ffmi_model *m, int which, int layer, float *out, long cap);
 long ffmi_model_debug_width(ffmi_model *m, int which);
 /* Negative-control fault injection (tests only; never set in serving): the
@@ -617,9 +662,10 @@ long ffmi_debug_markers(long long *dst, long n);
 const char *ffmi_status_str(ffmi_status s);
 /* message + file:line of the last failing check on this process */
 const char *ffmi_last_error(void);
-/* "ffmi 0.3 (gfx950)": 0.2 appended full_precision to ffmi_attn_cfg and
+/* "ffmi 0.4 (gfx950)": 0.2 appended full_precision to ffmi_attn_cfg and
  * ffmi_model_opts (struct sizes changed) and added the *_f32 entry points;
- * 0.3 appended spec_extensions to ffmi_rm_config */
+ * 0.3 appended spec_extensions to ffmi_rm_config; 0.4 added top-p sampling
+ * (ffmi_sample_topp, ffmi_sampling_counter, ffmi_model_set_sampling) */
 const char *ffmi_version(void);
 
 #ifdef __cplusplus
