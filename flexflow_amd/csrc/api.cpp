@@ -45,7 +45,9 @@ extern "C" const char *ffmi_status_str(ffmi_status s) {
 // 0.2: ffmi_attn_cfg.full_precision and ffmi_model_opts.full_precision
 // appended (struct sizes changed), the *_f32 entry points added
 // 0.3: ffmi_rm_config.spec_extensions
-// 0.4: top-p sampling (ffmi_sample_topp, ffmi_sampling_counter, ffmi_model_set_sampling)
+// 0.4: top-p sampling (ffmi_sample_topp, ffmi_sampling_counter, ffmi_model_set_sampling);
+// then, with no change to anything there before (the string stays), its
+// vocab-sharded form: ffmi_vocab_shard_sample_scratch_bytes, ffmi_vocab_shard_sample_topp
 extern "C" const char *ffmi_version(void) { return "ffmi 0.4 (gfx950)"; }
 
 // ---------------------------------------------------------------------------
@@ -1116,6 +1118,72 @@ extern "C" ffmi_status ffmi_vocab_shard_topk(ffmi_comm *c, const void *logits, i
   }
   FFMI_HIP(ffmi::launch_vshard((const uint16_t *)logits, T, Vl, P, c->rank, k, 3, x, kVshardW,
                                ids, probs, s));
+  return FFMI_OK;
+}
+
+// Vocab-sharded top-p sampling (norm.hip vshard_sample_kernel): six launches
+// and five record exchanges per chunk of rows.  The sum-as-gather moves P x
+// the payload, so the rows go in chunks that keep every exchange within
+// kVshardSampleMaxExchangeBytes: inside the 1 MiB exchange buffers of small
+// models and of what the xGMI transport takes in one kernel.
+static constexpr size_t kVshardSampleMaxExchangeBytes = 256u << 10;
+static int vshard_sample_max_rows(int P) {  // 256 / P: 32 rows at P = 8
+  return (int)(kVshardSampleMaxExchangeBytes /
+               ((size_t)P * ffmi::vshard_sample_max_record_floats() * sizeof(float)));
+}
+static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+extern "C" size_t ffmi_vocab_shard_sample_scratch_bytes(int nranks, int T, int Vl) {
+  if (nranks <= 0 || T <= 0 || Vl <= 0 || vshard_sample_max_rows(nranks) < 1) return 0;
+  const size_t rows = (size_t)std::min(T, vshard_sample_max_rows(nranks));
+  return align256((size_t)T * Vl * sizeof(uint16_t)) + align256(ffmi::vshard_sample_state_bytes(T)) +
+         2 * (size_t)nranks * rows * ffmi::vshard_sample_max_record_floats() * sizeof(float);
+}
+
+extern "C" ffmi_status ffmi_vocab_shard_sample_topp(ffmi_comm *c, const void *logits, int T,
+                                                    int Vl, float temperature, float topp,
+                                                    const float *u, int32_t *ids, float *probs,
+                                                    void *scratch, size_t scratch_bytes,
+                                                    ffmi_stream stream) {
+  FFMI_CHECK(c && logits && u && ids && T >= 0 && Vl >= 1, FFMI_ERR_INVALID);
+  FFMI_CHECK(temperature > 0.f && topp > 0.f && topp <= 1.f, FFMI_ERR_INVALID);  // (NaN: invalid)
+  FFMI_CHECK(Vl <= 983040 && ((size_t)c->rank + 1) * (size_t)Vl <= 0x7fffffffu &&
+                 vshard_sample_max_rows(c->nranks) >= 1,
+             FFMI_ERR_UNSUPPORTED);
+  // (16-byte aligned: the transport moves the records as 16-byte vectors)
+  FFMI_CHECK(T == 0 || (scratch && ((size_t)scratch & 15) == 0 &&
+                        scratch_bytes >= ffmi_vocab_shard_sample_scratch_bytes(c->nranks, T, Vl)),
+             FFMI_ERR_INVALID);
+  if (T == 0) return FFMI_OK;
+  const hipStream_t s = (hipStream_t)stream;
+  const int P = c->nranks;
+  int chunk = vshard_sample_max_rows(P);
+  // A/B runs and tests: fewer rows per chunk (the same value on every rank)
+  if (const char *e = getenv("FFMI_VSHARD_SAMPLE_CHUNK_ROWS"))
+    if (atoi(e) >= 1) chunk = std::min(chunk, atoi(e));
+  char *base = (char *)scratch;
+  uint16_t *keys = (uint16_t *)base;
+  unsigned *state = (unsigned *)(base + align256((size_t)T * Vl * sizeof(uint16_t)));
+  // two record buffers: a phase reads the one the phase before it wrote
+  float *x[2];
+  x[0] = (float *)((char *)state + align256(ffmi::vshard_sample_state_bytes(T)));
+  x[1] = x[0] + (size_t)P * std::min(T, vshard_sample_max_rows(P)) *
+                    ffmi::vshard_sample_max_record_floats();
+  for (int row0 = 0; row0 < T; row0 += chunk) {
+    const int rows = std::min(chunk, T - row0);
+    for (int phase = 0; phase < 5; ++phase) {
+      float *xo = x[phase & 1];
+      FFMI_HIP(ffmi::launch_vshard_sample((const uint16_t *)logits, Vl, P, c->rank, row0, rows,
+                                          phase, temperature, topp, u, keys, state,
+                                          x[(phase & 1) ^ 1], xo, nullptr, nullptr, s));
+      const ffmi_status st = ffmi_allreduce(
+          c, xo, xo, (size_t)P * rows * ffmi::vshard_sample_record_floats(phase), FFMI_F32, stream);
+      if (st != FFMI_OK) return st;
+    }
+    FFMI_HIP(ffmi::launch_vshard_sample((const uint16_t *)logits, Vl, P, c->rank, row0, rows, 5,
+                                        temperature, topp, u, keys, state, x[0], x[1], ids, probs,
+                                        s));
+  }
   return FFMI_OK;
 }
 

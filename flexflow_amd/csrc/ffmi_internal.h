@@ -256,6 +256,19 @@ size_t sample_topp_workspace_bytes(int T, int V);
 hipError_t launch_vshard(const uint16_t *logits, int T, int Vl, int P, int rank, int k,
                          int phase, float *xch, int W, int32_t *ids, float *probs,
                          hipStream_t s);
+// Vocab-sharded top-p sampling (norm.hip vshard_sample_kernel): phase 0..4
+// write this rank's records of rows [row0, row0 + rows) into xout
+// ([P][rows][vshard_sample_record_floats(phase)] floats, to be sum-all-reduced
+// and passed as xin -- another buffer -- to the next phase), phase 5 writes
+// ids / probs.  keys: [T][Vl] halves, state: vshard_sample_state_bytes(T),
+// both kept from phase to phase.
+hipError_t launch_vshard_sample(const uint16_t *logits, int Vl, int P, int rank, int row0,
+                                int rows, int phase, float temperature, float topp,
+                                const float *u, uint16_t *keys, unsigned *state, const float *xin,
+                                float *xout, int32_t *ids, float *probs, hipStream_t s);
+int vshard_sample_record_floats(int phase);
+int vshard_sample_max_record_floats();
+size_t vshard_sample_state_bytes(int T);
 hipError_t launch_group_sum(const void *const *bufs, int n, void *out, size_t count, int dtype,
                             hipStream_t s);
 

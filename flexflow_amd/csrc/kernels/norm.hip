@@ -1175,6 +1175,305 @@ hipError_t launch_vshard(const uint16_t *logits, int T, int Vl, int P, int rank,
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// Vocab-sharded top-p sampling: sample_topp_kernel's rule on logits that stay
+// sharded ([T][Vl] per rank, ids [rank*Vl, (rank+1)*Vl)).  The masses are
+// integers (multiples of 2^-24), so their sums do not depend on how the
+// vocabulary is split, and every rank derives the same pick from small
+// per-row records -- five exchanges, never the logits:
+//   phase 0: z = half(x / half(temperature)) into the row's key workspace,
+//            local max                       -> exchange -> M = max over ranks
+//   phase 1: local double sum of exp(z - M)  -> exchange -> S = float(sum)
+//   phase 2: key = half(exp(z - M) / S) replaces z; the 15361-key LDS mass
+//            histogram, summed into the 121 buckets key >> 7; the rank's last
+//            token of the order (lowest key, highest index)
+//                                            -> exchange -> the bucket B at
+//            which the cumulative mass from the top reaches the target (none:
+//            the row falls back to the last token over the ranks)
+//   phase 3: tokens per key for the 128 keys of B -> exchange -> the key K,
+//            the rank r of the pick among K's tokens in global index order,
+//            the owner (first rank whose prefix of counts exceeds r)
+//   phase 4: the owner finds its (r - prefix)-th token holding K (the ballot
+//            counts of sample_topp_kernel)   -> exchange -> the global id
+//   phase 5: ids / probs on every rank.
+// Exchange records are [P][rows][W] floats, W per phase (kVsW): a rank writes
+// its own slot and zeroes the others, the sum all-reduce is an all-gather.
+// Every value sent is an integer below 2^24 or a float sent as is (masses and
+// ids go as v >> 12 and v & 4095), so x + 0 = x holds exactly.  What a row
+// needs from one launch to the next and every rank derives alike (M, target,
+// B, the mass above B, the fallback token, K) is kept in `state`, local memory
+// that is not exchanged.  The workspace element i is only touched by thread
+// i % TPB.  A phase's record width differs from the one before it, so a
+// workgroup's slots would overlap another row's unread ones in one buffer: the
+// records alternate between two buffers (a launch reads xin, the all-reduced
+// records of the phase before, and writes xout).
+// ---------------------------------------------------------------------------
+constexpr int kVsBuckets = (kSampleKeys + 127) / 128;  // 121
+// (multiples of 4 floats: the transport moves 16-byte vectors)
+constexpr int kVsUsed[5] = {1, 2, 2 * kVsBuckets + 3, 128, 2};
+constexpr int kVsW[5] = {4, 4, (kVsUsed[2] + 3) & ~3, 128, 4};
+constexpr int kVsMaxW = 256;
+enum { VS_M, VS_TARGET, VS_FALLBACK, VS_B, VS_C, VS_FB_ID, VS_FB_KEY, VS_K, kVsState };
+static_assert(kVsW[2] <= kVsMaxW && kVsW[3] <= kVsMaxW, "exchange record width");
+
+__device__ __forceinline__ void vs_put(float *p, unsigned v) {
+  p[0] = (float)(v >> 12), p[1] = (float)(v & 4095u);
+}
+__device__ __forceinline__ unsigned vs_get(const float *p) {
+  return (unsigned)p[0] * 4096u + (unsigned)p[1];
+}
+
+template <int TPB, int PHASE>
+__global__ __launch_bounds__(TPB) void vshard_sample_kernel(
+    const uint16_t *__restrict__ logits, int Vl, int P, int rank, int row0, float temperature,
+    float topp, const float *__restrict__ u, uint16_t *__restrict__ kws,
+    unsigned *__restrict__ state, const float *__restrict__ xin, float *__restrict__ xout,
+    int32_t *__restrict__ ids, float *__restrict__ probs) {
+  constexpr int NW = TPB / 64;
+  constexpr int WR = kVsW[PHASE > 0 ? PHASE - 1 : 0];  // records read
+  constexpr int WW = kVsW[PHASE < 5 ? PHASE : 4];      // records written
+  const int b = blockIdx.x, n = gridDim.x, t = row0 + b;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const uint16_t *x = logits + (size_t)t * Vl;
+  uint16_t *w = kws + (size_t)t * Vl;
+  unsigned *st = state + (size_t)t * kVsState;
+  auto rd = [&](int r) -> const float * { return xin + ((size_t)r * n + b) * WR; };
+  auto wr = [&](int r) -> float * { return xout + ((size_t)r * n + b) * WW; };
+  float *own = wr(rank);
+  // the other ranks' slots and this slot from `used` on (a loop: the records
+  // are wider than the workgroup at P * WW > TPB)
+  auto zero_slots = [&](int used) {
+    for (int q = tid; q < P * WW; q += TPB) {
+      const int r = q / WW;
+      if (r != rank || q - r * WW >= used) wr(r)[q - r * WW] = 0.f;
+    }
+  };
+  (void)lane, (void)wv, (void)x, (void)w, (void)rd, (void)own, (void)zero_slots;
+
+  if constexpr (PHASE == 0) {
+    __shared__ float fsh[NW];
+    const float th = h2f_(f2h_(temperature));
+    float mx = -INFINITY;
+    for (int i = tid; i < Vl; i += TPB) {
+      const uint16_t z = f2h_(__fdiv_rn(h2f_(x[i]), th));
+      w[i] = z;
+      mx = fmaxf(mx, h2f_(z));
+    }
+    mx = __ockl_wfred_max_f32(mx);
+    if (lane == 0) fsh[wv] = mx;
+    __syncthreads();
+    float M = fsh[0];
+#pragma unroll
+    for (int q = 1; q < NW; ++q) M = fmaxf(M, fsh[q]);
+    zero_slots(kVsUsed[0]);
+    if (tid == 0) own[0] = M;
+  } else if constexpr (PHASE == 1) {
+    __shared__ double dsh[NW];
+    float M = -INFINITY;
+    for (int r = 0; r < P; ++r) M = fmaxf(M, rd(r)[0]);
+    double se = 0.0;
+    for (int i = tid; i < Vl; i += TPB) se += (double)expf_ref(h2f_(w[i]) - M);
+    se = __ockl_wfred_add_f64(se);
+    if (lane == 0) dsh[wv] = se;
+    __syncthreads();  // (also: every thread has read the phase-0 records)
+    se = 0.0;
+#pragma unroll
+    for (int q = 0; q < NW; ++q) se += dsh[q];
+    zero_slots(kVsUsed[1]);
+    if (tid == 0) {
+      const float hi = (float)se;
+      own[0] = hi, own[1] = (float)(se - (double)hi);
+      st[VS_M] = __float_as_uint(M);
+    }
+  } else if constexpr (PHASE == 2) {
+    __shared__ unsigned hist[kSampleKeys];
+    __shared__ unsigned long long ksh[NW];
+    for (int i = tid; i < kSampleKeys; i += TPB) hist[i] = 0;
+    double sd = 0.0;
+    for (int r = 0; r < P; ++r) sd += (double)rd(r)[0] + (double)rd(r)[1];
+    const float S = (float)sd, M = __uint_as_float(st[VS_M]);
+    __syncthreads();  // (also: every thread has read the phase-1 records)
+    // this rank's last token of the order: the largest (~key, local index)
+    unsigned long long lastk = 0;
+    for (int i = tid; i < Vl; i += TPB) {
+      const unsigned key = f2h_(__fdiv_rn(expf_ref(h2f_(w[i]) - M), S));
+      w[i] = (uint16_t)key;
+      // (a NaN row -- an infinite logit -- has keys outside the histogram: no mass)
+      if (key < (unsigned)kSampleKeys && key) atomicAdd(&hist[key], p_mass(key));
+      const unsigned long long lk = ((unsigned long long)(0xffffu - key) << 32) | (unsigned)i;
+      lastk = lk > lastk ? lk : lastk;
+    }
+    lastk = __ockl_wfred_max_u64(lastk);
+    if (lane == 0) ksh[wv] = lastk;
+    __syncthreads();
+    // the mass of each bucket key >> 7, a wave per bucket
+    for (int bk = wv; bk < kVsBuckets; bk += NW) {
+      const int k0 = bk * 128 + lane, k1 = k0 + 64;
+      unsigned m = (k0 < kSampleKeys ? hist[k0] : 0u) + (k1 < kSampleKeys ? hist[k1] : 0u);
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) m += __shfl_xor(m, o);
+      if (lane == 0) vs_put(own + 2 * bk, m);
+    }
+    zero_slots(kVsUsed[2]);
+    if (tid == 0) {
+#pragma unroll
+      for (int q = 0; q < NW; ++q) lastk = ksh[q] > lastk ? ksh[q] : lastk;
+      own[2 * kVsBuckets] = (float)(0xffffu - (unsigned)(lastk >> 32));
+      vs_put(own + 2 * kVsBuckets + 1, (unsigned)rank * (unsigned)Vl + (unsigned)(lastk & 0xffffffffu));
+    }
+  } else if constexpr (PHASE == 3) {
+    __shared__ unsigned coarse[128], cnt[128], wsum[NW];
+    __shared__ int res[2];
+    if (tid < 128) {
+      unsigned m = 0;
+      if (tid < kVsBuckets)
+        for (int r = 0; r < P; ++r) m += vs_get(rd(r) + 2 * tid);
+      coarse[tid] = m, cnt[tid] = 0;
+    }
+    // the last token of the order over the ranks: lowest key, highest id
+    unsigned fb_key = 0xffffffffu, fb_id = 0;
+    if (tid == 0)
+      for (int r = 0; r < P; ++r) {
+        const unsigned key = (unsigned)rd(r)[2 * kVsBuckets];
+        if (key <= fb_key) fb_key = key, fb_id = vs_get(rd(r) + 2 * kVsBuckets + 1);
+      }
+    // t * 2^24 rounded up: the smallest integer mass that reaches t
+    unsigned target;
+    {
+      const double tt = __dmul_rn(__dmul_rn((double)u[t], (double)topp), (double)topp);
+      const double tm = ceil(__dmul_rn(tt, 16777216.0));
+      target = tm >= 1.0 ? (tm < 4.0e9 ? (unsigned)tm : 4000000000u) : 1u;
+    }
+    __syncthreads();  // (also: the phase-2 records are read)
+    block_find<TPB, true>(coarse, kVsBuckets, target, wsum, res);
+    const int kq = res[0];
+    const unsigned B = (unsigned)(kVsBuckets - 1 - kq);
+    if (kq >= 0) {  // (uniform) this rank's tokens per key of bucket B, one add per wave and key
+      const int nchunk = (Vl + TPB - 1) / TPB;
+      for (int j = 0; j < nchunk; ++j) {
+        const int i = j * TPB + tid;
+        const unsigned key = i < Vl ? w[i] : 0xffffu;
+        const bool in = key < (unsigned)kSampleKeys && (key >> 7) == B;
+        unsigned long long m = __ballot(in);
+        while (m) {
+          const int l = __ffsll((long long)m) - 1;
+          const unsigned k0 = __shfl(key, l);
+          const unsigned long long same = __ballot(in && key == k0);
+          if (lane == l) atomicAdd(&cnt[k0 & 127u], (unsigned)__popcll(same));
+          m &= ~same;
+        }
+      }
+    }
+    __syncthreads();
+    zero_slots(kVsUsed[3]);
+    if (tid < 128) own[tid] = (float)cnt[tid];  // (<= Vl < 2^24)
+    if (tid == 0) {
+      st[VS_TARGET] = target, st[VS_FALLBACK] = kq < 0, st[VS_B] = B, st[VS_C] = (unsigned)res[1];
+      st[VS_FB_ID] = fb_id, st[VS_FB_KEY] = fb_key;
+    }
+  } else if constexpr (PHASE == 4) {
+    __shared__ unsigned hist[kSampleKeys];  // the counts per 64 consecutive indices
+    __shared__ unsigned fm[128], wsum[NW];
+    __shared__ int res[2];
+    const bool fallback = st[VS_FALLBACK] != 0;
+    const unsigned B = st[VS_B], target = st[VS_TARGET], c = st[VS_C];
+    if (tid < 128) {  // the mass of each key of bucket B over the ranks
+      unsigned tot = 0;
+      for (int r = 0; r < P; ++r) tot += (unsigned)rd(r)[tid];
+      const unsigned key = B * 128u + (unsigned)tid;
+      fm[tid] = !fallback && key < (unsigned)kSampleKeys ? tot * p_mass(key) : 0u;
+    }
+    __syncthreads();
+    int owner = -1;
+    unsigned K = 0, rloc = 0;
+    if (!fallback) {  // (uniform)
+      block_find<TPB, true>(fm, 128, target - c, wsum, res);
+      const int kq = res[0];
+      if (kq >= 0) {
+        K = B * 128u + 127u - (unsigned)kq;
+        const unsigned pm = p_mass(K);
+        // 0-based, among K's tokens in global index order
+        const unsigned rk = (target - c - (unsigned)res[1] + pm - 1) / pm - 1;
+        unsigned pre = 0;
+        for (int r = 0; r < P; ++r) {
+          const unsigned ck = (unsigned)rd(r)[K & 127u];
+          if (owner < 0 && rk - pre < ck) owner = r, rloc = rk - pre;
+          pre += ck;
+        }
+      }
+    }
+    __syncthreads();  // (every thread has read res and the phase-3 records)
+    zero_slots(0);
+    if (tid == 0) {
+      st[VS_K] = K;
+      if (owner < 0) st[VS_FALLBACK] = 1;  // (only a row outside the contract gets here)
+    }
+    if (owner == rank) {  // (uniform)
+      const int nchunk = (Vl + TPB - 1) / TPB;
+      for (int j = 0; j < nchunk; ++j) {
+        const int i = j * TPB + tid;
+        const unsigned long long bl = __ballot(i < Vl && w[i] == (uint16_t)K);
+        if (lane == 0) hist[j * NW + wv] = (unsigned)__popcll(bl);
+      }
+      __syncthreads();
+      block_find<TPB, false>(hist, nchunk * NW, rloc + 1, wsum, res);  // (barriers: after the zeroing)
+      const int g = res[0];
+      if (g >= 0 && g % NW == wv) {
+        const int i = (g / NW) * TPB + tid;
+        const bool hit = i < Vl && w[i] == (uint16_t)K;
+        const unsigned long long bl = __ballot(hit);
+        const unsigned below = (unsigned)__popcll(bl & ((1ull << lane) - 1ull));
+        if (hit && below == rloc - (unsigned)res[1])
+          vs_put(own, (unsigned)rank * (unsigned)Vl + (unsigned)i);
+      }
+    }
+  } else {
+    if (tid == 0) {
+      unsigned id = 0, key = st[VS_K];
+      if (st[VS_FALLBACK]) {
+        id = st[VS_FB_ID], key = st[VS_FB_KEY];
+      } else {
+        for (int r = 0; r < P; ++r) id += vs_get(rd(r));
+      }
+      ids[t] = (int32_t)id;
+      if (probs) probs[t] = h2f_((uint16_t)key);
+    }
+  }
+}
+
+int vshard_sample_record_floats(int phase) { return phase >= 0 && phase < 5 ? kVsW[phase] : 0; }
+int vshard_sample_max_record_floats() { return kVsMaxW; }
+size_t vshard_sample_state_bytes(int T) {
+  return T <= 0 ? 0 : (size_t)T * kVsState * sizeof(unsigned);
+}
+
+hipError_t launch_vshard_sample(const uint16_t *logits, int Vl, int P, int rank, int row0,
+                                int rows, int phase, float temperature, float topp,
+                                const float *u, uint16_t *keys, unsigned *state, const float *xin,
+                                float *xout, int32_t *ids, float *probs, hipStream_t s) {
+  if (rows <= 0) return hipSuccess;
+  if (Vl < 1 || Vl > kSampleMaxV || P < 1 || rank < 0 || rank >= P || !keys || !state || !xin ||
+      !xout || xin == xout)
+    return hipErrorInvalidValue;
+#define FFMI_VS(PH)                                                                             \
+  case PH:                                                                                      \
+    hipLaunchKernelGGL((vshard_sample_kernel<kSampleTPB, PH>), dim3(rows), dim3(kSampleTPB), 0, \
+                       s, logits, Vl, P, rank, row0, temperature, topp, u, keys, state, xin,    \
+                       xout, ids, probs);                                                       \
+    break
+  switch (phase) {
+    FFMI_VS(0);
+    FFMI_VS(1);
+    FFMI_VS(2);
+    FFMI_VS(3);
+    FFMI_VS(4);
+    FFMI_VS(5);
+    default: return hipErrorInvalidValue;
+  }
+#undef FFMI_VS
+  return hipGetLastError();
+}
+
 // Sum of the ranks' buffers of an in-process shard group (ffmi_comm_create_
 // local): out = sum over r in rank order, fp16 accumulated in fp32 then
 // rounded once (RCCL's ring sums in fp16 in ring order; both are within an

@@ -69,21 +69,29 @@ struct LlamaGPU : public ffmi_model {
   bool sampling = false;
   float temperature = 0.8f, topp = 0.6f;
   uint64_t sampling_seed = 0;
-  uint16_t *sample_ws = nullptr;  // [Tm][V], allocated when sampling is first turned on
+  // [Tm][V] keys, or, under a vocab-sharded lm_head, the scratch of
+  // ffmi_vocab_shard_sample_topp ([Tm][Vl] keys + exchange records);
+  // allocated when sampling is first turned on
+  uint16_t *sample_ws = nullptr;
+  size_t sample_ws_bytes = 0;
   std::vector<float> step_u;
   size_t step_u_off = 0;
   ffmi_status set_sampling(bool on, float temp, float p, uint64_t seed) override {
     const char *why = mode != FFMI_MODEL_INC
                           ? "sampling: a BEAM / TREE model decodes greedily (a sampled pick "
                             "cannot verify a greedy token tree)"
-                          : Vl != c.vocab_size ? "sampling: vocab-sharded lm_head" : nullptr;
+                          : Vl != c.vocab_size && !o.comm ? "sampling: vocab-sharded lm_head"
+                                                          : nullptr;
     if (why) {
       ffmi_set_last_error(why, __FILE__, __LINE__);
       return FFMI_ERR_UNSUPPORTED;
     }
     const size_t Tm = (size_t)((o.max_tokens + 15) & ~15);
     if (on && !sample_ws) {
-      const ffmi_status st = alloc(&sample_ws, Tm * c.vocab_size);
+      sample_ws_bytes = Vl != c.vocab_size ? ffmi_vocab_shard_sample_scratch_bytes(
+                                                 ffmi::comm_size(o.comm), (int)Tm, Vl)
+                                           : ffmi::sample_topp_workspace_bytes((int)Tm, Vl);
+      const ffmi_status st = alloc(&sample_ws, (sample_ws_bytes + 1) / 2);
       if (st != FFMI_OK) return st;
     }
     // (the captured graphs hold the tail's kernel and its scalar arguments)
@@ -1328,9 +1336,16 @@ struct LlamaGPU : public ffmi_model {
     // keeps the device buffer + copy (A/B runs)
     int32_t *ids_o = result_copy ? ids_d : ids_h + cur_slot * slot_ints();
     float *probs_o = reinterpret_cast<float *>(ids_o + (size_t)T * k);
-    if (sampling) {
-      // (set_sampling: INC, unsharded vocabulary; u behind the blob's records)
-      FFMI_CHECK(k == 1 && Vl == V && sample_ws, FFMI_ERR_INVALID);
+    if (sampling && Vl != V) {
+      // sharded top-p: five record exchanges; every rank staged the same u
+      FFMI_CHECK(k == 1 && sample_ws, FFMI_ERR_INVALID);
+      TRY(ffmi_vocab_shard_sample_topp(
+          o.comm, logits, T, Vl, temperature, topp,
+          reinterpret_cast<const float *>(batch->dev + step_u_off), ids_o, probs_o, sample_ws,
+          sample_ws_bytes, s));
+    } else if (sampling) {
+      // (set_sampling: INC; u behind the blob's records)
+      FFMI_CHECK(k == 1 && sample_ws, FFMI_ERR_INVALID);
       FFMI_HIP(ffmi::launch_sample_topp(
           logits, T, V, temperature, topp, reinterpret_cast<const float *>(batch->dev + step_u_off),
           ids_o, probs_o, sample_ws, ffmi::sample_topp_workspace_bytes(T, V), stream));

@@ -164,6 +164,10 @@ SIGNATURES = {
     "ffmi_vocab_shard_scratch_bytes": (c_size_t, [c_int, c_int]),
     "ffmi_vocab_shard_topk": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
                                       c_void_p, c_void_p, c_void_p]),
+    "ffmi_vocab_shard_sample_scratch_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "ffmi_vocab_shard_sample_topp": (c_int, [c_void_p, c_void_p, c_int, c_int, c_float, c_float,
+                                             c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                             c_void_p]),
     "ffmi_allreduce": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
     "ffmi_allreduce_rmsnorm": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                                        c_void_p, c_float, c_void_p, c_int, c_void_p, c_void_p]),

@@ -64,9 +64,12 @@ class Model:
         uniform of token `pos` of request `guid` (ffmi.sampling_counter(seed,
         guid, pos) + 1) * 2**-24, pos the token's index in the request's
         sequence -- the draws depend on the seed, not on the batching.  None
-        or do_sample False: greedy decoding.  FFMIError
-        (unsupported) on a "beam" / "tree" model, a full_precision model and a
-        vocab-sharded lm_head (ffmi_model_set_sampling)."""
+        or do_sample False: greedy decoding.  Works at tp_size > 1 too, with a
+        vocab-sharded lm_head included: set the same config and seed on every
+        rank's shard, and every rank emits the same tokens, those of the rule
+        on the gathered logits (ffmi_vocab_shard_sample_topp).  FFMIError
+        (unsupported) on a "beam" / "tree" model and a full_precision model
+        (ffmi_model_set_sampling)."""
         gc = generation_config or GenerationConfig()
         F.check(F.lib().ffmi_model_set_sampling(self.handle, int(bool(gc.do_sample)),
                                                 float(gc.temperature), float(gc.topp),

@@ -263,6 +263,37 @@ ffmi_status ffmi_allreduce(ffmi_comm *c, const void *in, void *out, size_t count
 size_t ffmi_vocab_shard_scratch_bytes(int nranks, int T);
 ffmi_status ffmi_vocab_shard_topk(ffmi_comm *c, const void *logits, int T, int Vl, int k,
                                   int32_t *ids, float *probs, void *scratch, ffmi_stream stream);
+/* Vocab-parallel top-p sampling: the do_sample tail (ffmi_sample_topp, below)
+ * on the same sharded logits.  Every rank gets, per row, the token and the p
+ * that ffmi_sample_topp returns on the gathered [T][P*Vl] logits with the same
+ * temperature, topp and u -- the same token, not an approximation: the rule's
+ * cumulative masses are integer multiples of 2^-24, so they do not depend on
+ * how the vocabulary is split.  The logits are never gathered: five exchanges
+ * of per-row records (the max, the sum of the exp terms, a 121-bucket mass
+ * histogram, the token counts of one bucket's 128 keys, the owner's id) go
+ * over the communicator as sum all-reduces, between six kernel launches.  No
+ * exchange exceeds 256 KiB: rows are processed in chunks of 256 / P rows (32
+ * at P = 8; FFMI_VSHARD_SAMPLE_CHUNK_ROWS, read per call, lowers it for A/B
+ * runs and must be the same on every rank), all phases per chunk.
+ * `u` is device memory, one uniform in (0, 1] per row, and MUST hold the same
+ * values on every rank: that is the caller's duty (ffmi_sampling_counter is a
+ * function of seed, request and position only, so ranks that see the same
+ * batch draw alike without an exchange).  ids / probs may be pinned host
+ * memory, probs may be NULL.  `scratch` is 16-byte aligned device memory of
+ * ffmi_vocab_shard_sample_scratch_bytes(P, T, Vl) bytes (the [T][Vl] fp16 key
+ * workspace, per-row state and the exchange records; any contents on entry),
+ * one per stream in flight.  Kernel launches and ffmi_allreduce calls on
+ * `stream` only: graph-capturable like ffmi_vocab_shard_topk.
+ * Decided before any HIP call -- FFMI_ERR_INVALID: a null c / logits / u /
+ * ids, T < 0, Vl < 1, temperature <= 0, topp outside (0, 1], a missing or too
+ * small scratch; FFMI_ERR_UNSUPPORTED: Vl > 983040, (rank + 1) * Vl > 2^31 - 1.
+ * T == 0 is FFMI_OK.  Rows with NaN or +inf logits are outside the contract
+ * (any in-range or out-of-range id may come back; nothing faults). */
+size_t ffmi_vocab_shard_sample_scratch_bytes(int nranks, int T, int Vl);
+ffmi_status ffmi_vocab_shard_sample_topp(ffmi_comm *c, const void *logits, int T, int Vl,
+                                         float temperature, float topp, const float *u,
+                                         int32_t *ids, float *probs, void *scratch,
+                                         size_t scratch_bytes, ffmi_stream stream);
 
 #define FFMI_PEER_HANDLE_BYTES 64
 ffmi_status ffmi_comm_create_peer(int nranks, int rank, ffmi_comm **out);
@@ -491,11 +522,14 @@ ffmi_status ffmi_model_set_debug(ffmi_model *m, int enable);
  * (inference.h:22-33, llama.cc:284-295).  do_sample != 0: an incremental-
  * decoding model picks every token with ffmi_sample_topp instead of the
  * argmax, u = (ffmi_sampling_counter(seed, request guid, position) + 1) *
- * 2^-24.  temperature <= 0 becomes 0.8 and topp <= 0 becomes 0.6, as the
- * reference's constructor; topp > 1 is FFMI_ERR_INVALID.  do_sample == 0
- * restores the greedy tail.  FFMI_ERR_UNSUPPORTED (message in
+ * 2^-24.  A tensor-parallel model with a vocab-sharded lm_head takes
+ * ffmi_vocab_shard_sample_topp over its communicator: the same tokens on
+ * every rank (each rank draws the same u from the same batch), the steps
+ * still replayed as graphs.  temperature <= 0 becomes 0.8 and topp <= 0
+ * becomes 0.6, as the reference's constructor; topp > 1 is FFMI_ERR_INVALID.
+ * do_sample == 0 restores the greedy tail.  FFMI_ERR_UNSUPPORTED (message in
  * ffmi_last_error) for a BEAM or TREE model (a sampled pick cannot verify a
- * greedy token tree), a full_precision model and a vocab-sharded lm_head. */
+ * greedy token tree) and a full_precision model. */
 ffmi_status ffmi_model_set_sampling(ffmi_model *m, int do_sample, float temperature, float topp,
                                     uint64_t seed);
 long ffmi_model_debug_tensor(ffmi_model *m, int which, int layer, float *out, long cap);
@@ -665,7 +699,10 @@ const char *ffmi_last_error(void);
 /* "ffmi 0.4 (gfx950)": 0.2 appended full_precision to ffmi_attn_cfg and
  * ffmi_model_opts (struct sizes changed) and added the *_f32 entry points;
  * 0.3 appended spec_extensions to ffmi_rm_config; 0.4 added top-p sampling
- * (ffmi_sample_topp, ffmi_sampling_counter, ffmi_model_set_sampling) */
+ * (ffmi_sample_topp, ffmi_sampling_counter, ffmi_model_set_sampling) and,
+ * later under the same string (nothing that existed changed), its vocab-
+ * sharded form: ffmi_vocab_shard_sample_scratch_bytes and
+ * ffmi_vocab_shard_sample_topp */
 const char *ffmi_version(void);
 
 #ifdef __cplusplus
