@@ -1093,7 +1093,7 @@ ffmi_status comm_status(ffmi_comm *c) {
 
 // Vocab-sharded softmax + argmax / arg-top-k (model.cc:3392-3419 Combine of
 // the vocab-parallel lm_head, then argmax.cu:62-100 / arg_topk.cu:339-448):
-// three record exchanges over the communicator (norm.hip vshard_kernel).
+// three record exchanges over the communicator (sampling.hip vshard_kernel).
 static constexpr int kVshardW = 8;  // floats per (rank, row) record
 extern "C" size_t ffmi_vocab_shard_scratch_bytes(int nranks, int T) {
   return nranks > 0 && T > 0 ? (size_t)nranks * T * kVshardW * sizeof(float) : 0;
@@ -1121,7 +1121,7 @@ extern "C" ffmi_status ffmi_vocab_shard_topk(ffmi_comm *c, const void *logits, i
   return FFMI_OK;
 }
 
-// Vocab-sharded top-p sampling (norm.hip vshard_sample_kernel): six launches
+// Vocab-sharded top-p sampling (sampling.hip vshard_sample_kernel): six launches
 // and five record exchanges per chunk of rows.  The sum-as-gather moves P x
 // the payload, so the rows go in chunks that keep every exchange within
 // kVshardSampleMaxExchangeBytes: inside the 1 MiB exchange buffers of small
@@ -1147,7 +1147,7 @@ extern "C" ffmi_status ffmi_vocab_shard_sample_topp(ffmi_comm *c, const void *lo
                                                     ffmi_stream stream) {
   FFMI_CHECK(c && logits && u && ids && T >= 0 && Vl >= 1, FFMI_ERR_INVALID);
   FFMI_CHECK(temperature > 0.f && topp > 0.f && topp <= 1.f, FFMI_ERR_INVALID);  // (NaN: invalid)
-  FFMI_CHECK(Vl <= 983040 && ((size_t)c->rank + 1) * (size_t)Vl <= 0x7fffffffu &&
+  FFMI_CHECK(Vl <= ffmi::sample_topp_max_v() && ((size_t)c->rank + 1) * (size_t)Vl <= 0x7fffffffu &&
                  vshard_sample_max_rows(c->nranks) >= 1,
              FFMI_ERR_UNSUPPORTED);
   // (16-byte aligned: the transport moves the records as 16-byte vectors)

@@ -238,6 +238,11 @@ hipError_t launch_embedding(const char *blob, int T, const uint16_t *table,
                             uint16_t *out, int H, hipStream_t s);
 hipError_t launch_silu_mul(const uint16_t *a, const uint16_t *b, uint16_t *out,
                            size_t n, hipStream_t s);
+hipError_t launch_group_sum(const void *const *bufs, int n, void *out, size_t count, int dtype,
+                            hipStream_t s);
+
+// kernels/sampling.hip: the fp16 token pick -- softmax + argmax / top-k, top-p
+// sampling, and both on logits sharded over the vocabulary.
 // softmax + argmax / top-k; with a zeroed workspace of argmax_workspace_bytes(T)
 // (left zeroed) rows of a small T are split over several workgroups
 hipError_t launch_argmax(const uint16_t *logits, int T, int V, int k, int32_t *ids,
@@ -251,12 +256,13 @@ hipError_t launch_sample_topp(const uint16_t *logits, int T, int V, float temper
                               const float *u, int32_t *ids, float *probs, void *ws,
                               size_t ws_bytes, hipStream_t s);
 size_t sample_topp_workspace_bytes(int T, int V);
-// Vocab-sharded tail (norm.hip): phase 0..2 write this rank's exchange
+int sample_topp_max_v();  // the longest row (or shard of one) the sampling kernels take
+// Vocab-sharded tail (vshard_kernel): phase 0..2 write this rank's exchange
 // record ([P][T][W] floats, W >= max(4, 2k)); phase 3 merges into ids/probs.
 hipError_t launch_vshard(const uint16_t *logits, int T, int Vl, int P, int rank, int k,
                          int phase, float *xch, int W, int32_t *ids, float *probs,
                          hipStream_t s);
-// Vocab-sharded top-p sampling (norm.hip vshard_sample_kernel): phase 0..4
+// Vocab-sharded top-p sampling (vshard_sample_kernel): phase 0..4
 // write this rank's records of rows [row0, row0 + rows) into xout
 // ([P][rows][vshard_sample_record_floats(phase)] floats, to be sum-all-reduced
 // and passed as xin -- another buffer -- to the next phase), phase 5 writes
@@ -269,8 +275,6 @@ hipError_t launch_vshard_sample(const uint16_t *logits, int Vl, int P, int rank,
 int vshard_sample_record_floats(int phase);
 int vshard_sample_max_record_floats();
 size_t vshard_sample_state_bytes(int T);
-hipError_t launch_group_sum(const void *const *bufs, int n, void *out, size_t count, int dtype,
-                            hipStream_t s);
 
 hipError_t launch_kv_update(const char *blob, int T, int W, int C, const uint16_t *qkv,
                             Partials qkvp, uint16_t *qbuf, uint16_t *kc, uint16_t *vc,

@@ -1,5 +1,5 @@
 // expf_ref.h -- the host libm's expf restated for device code, shared by the
-// fp16 softmax / top-k (norm.hip) and the fp32 one (f32.hip).
+// fp16 softmax / top-k (sampling.hip) and the fp32 one (f32.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 

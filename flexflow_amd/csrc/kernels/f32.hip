@@ -2,7 +2,7 @@
 // (inference/spec_infer/spec_infer.cc:102, incr_decoding.cc:77), i.e. every
 // operator of the LLaMA graph on DT_FLOAT -- weights, activations, KV cache,
 // softmax.  The same operators as the half path (gemm.hip, attention.hip,
-// norm.hip), restated for fp32 operands:
+// norm.hip, sampling.hip), restated for fp32 operands:
 //  * Linear on v_mfma_f32_16x16x4_f32 -- exact fp32: the result is a k-ordered
 //    fmaf chain per (wave, k range), no reduced-precision inputs (gfx950 has
 //    no xf32), k ranges of a workgroup summed in a fixed order;

@@ -75,7 +75,11 @@ CFG4 = dict(num_layers=2, vocab_size=1000, num_heads=4, num_kv_heads=4, hidden=2
 
 
 @pytest.mark.parametrize("n,T,V,k", [(2, 168, 4096, 1), (4, 37, 32000, 3), (4, 168, 32000, 1),
-                                     (8, 24, 32000, 3)])
+                                     (8, 24, 32000, 3),
+                                     # shards of fewer than k logits: empty candidates on
+                                     # every rank; and one wave of data, so that the k-th
+                                     # largest wave maximum is -inf
+                                     (8, 5, 16, 4), (4, 5, 16, 3)])
 def test_vocab_shard_topk_matches_unsharded(n, T, V, k):
     """Vocab-parallel lm_head tail (model.cc:3392-3419): every rank's global
     top-k ids and fp16 probabilities are bit-identical to the oracle's softmax

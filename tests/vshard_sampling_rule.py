@@ -1,4 +1,4 @@
-"""The phase algorithm of ffmi_vocab_shard_sample_topp (norm.hip
+"""The phase algorithm of ffmi_vocab_shard_sample_topp (sampling.hip
 vshard_sample_kernel) restated in numpy on the fp16 keys of p: what each rank
 sends in the last three exchanges and what every rank derives from the sums.
 The integer arithmetic here is the kernel's; tests/sampling_rule.py is the rule
