@@ -14,6 +14,7 @@
 
 #include <algorithm>
 #include <climits>
+#include <cstddef>
 
 #include "ffmi_internal.h"
 #include "collective.h"
@@ -47,7 +48,8 @@ extern "C" const char *ffmi_status_str(ffmi_status s) {
 // 0.3: ffmi_rm_config.spec_extensions
 // 0.4: top-p sampling (ffmi_sample_topp, ffmi_sampling_counter, ffmi_model_set_sampling);
 // then, with no change to anything there before (the string stays), its
-// vocab-sharded form: ffmi_vocab_shard_sample_scratch_bytes, ffmi_vocab_shard_sample_topp
+// vocab-sharded form: ffmi_vocab_shard_sample_scratch_bytes, ffmi_vocab_shard_sample_topp,
+// and the ffmi_debug_*_partials / ffmi_debug_rmsnorm_gather test hooks
 extern "C" const char *ffmi_version(void) { return "ffmi 0.4 (gfx950)"; }
 
 // ---------------------------------------------------------------------------
@@ -239,12 +241,14 @@ extern "C" ffmi_status ffmi_batch_upload(ffmi_batch_dev *b, const ffmi_batch_des
 // attention handles
 // ---------------------------------------------------------------------------
 struct ffmi_attn {
-  ffmi_attn_cfg cfg;
+  ffmi_attn_cfg cfg;  // first: all ffmi_debug_attn_partials reads before it refuses
+                      // (tests/test_partials_cpu.py fabricates that much without a device)
   int slots = 0;
   uint16_t *kc = nullptr, *vc = nullptr, *qbuf = nullptr, *stage = nullptr;
   int parity = 0;  // TREE staging half written by the next public-API step
   float *rope = nullptr;
 };
+static_assert(offsetof(ffmi_attn, cfg) == 0, "ffmi_attn starts with its cfg (test_partials_cpu.py)");
 
 // cos/sin table, same arithmetic as the reference's apply_rotary_embedding_hf
 // (inc_multihead_self_attention.cu:701-725): freq = pos * (1.0 /
@@ -672,6 +676,91 @@ extern "C" ffmi_status ffmi_debug_fused_norm_linear(const void *residual, const 
   FFMI_HIP(ffmi::launch_gemm((const uint16_t *)residual, (const uint16_t *)W_packed, (uint16_t *)Y,
                              nullptr, 0, T, out_dim, in_dim, epilogue, (hipStream_t)stream,
                              nullptr, 0, &fz));
+  return FFMI_OK;
+}
+
+// Test hooks of the deferred split-K slab consumers (Partials: fp32 slabs
+// [S][T][NP], value = fp16 of the in-order sum): the in-library model's entry
+// points with caller-made slabs.  Every refusal is decided here, before any
+// HIP call, and covers what the launchers below would refuse.
+extern "C" ffmi_status ffmi_debug_partials_reduce(const float *slabs, int S, int NP, void *Y,
+                                                  int T, int N, ffmi_stream stream) {
+  FFMI_CHECK(slabs && Y && T >= 0 && ((size_t)slabs & 15) == 0, FFMI_ERR_INVALID);
+  FFMI_CHECK(S >= 1 && S <= 16 && NP > 0 && NP % 16 == 0 && N >= 1 && N <= NP, FFMI_ERR_INVALID);
+  ffmi::Partials p;
+  p.p = slabs, p.S = S, p.NP = NP;
+  FFMI_HIP(ffmi::launch_partials_reduce(p, (uint16_t *)Y, T, N, (hipStream_t)stream));
+  return FFMI_OK;
+}
+
+extern "C" ffmi_status ffmi_debug_rmsnorm_partials(const void *x1, const float *slabs, int S,
+                                                   int NP, const void *w, void *residual_out,
+                                                   void *out, int T, int H, float eps, int flags,
+                                                   ffmi_stream stream) {
+  FFMI_CHECK(x1 && slabs && w && out && T >= 0 && ((size_t)slabs & 15) == 0, FFMI_ERR_INVALID);
+  FFMI_CHECK(residual_out, FFMI_ERR_INVALID);
+  FFMI_CHECK(H >= 8 && H % 8 == 0 && H <= 8192, FFMI_ERR_INVALID);
+  FFMI_CHECK(S >= 1 && S <= 16 && (S <= 8 || H <= 1024), FFMI_ERR_INVALID);
+  FFMI_CHECK(NP >= H && NP % 4 == 0, FFMI_ERR_INVALID);
+  FFMI_CHECK((flags & ~FFMI_Y_PACKED) == 0, FFMI_ERR_INVALID);
+  const bool packed = (flags & FFMI_Y_PACKED) != 0;
+  FFMI_CHECK(!packed || H % 32 == 0, FFMI_ERR_UNSUPPORTED);
+  ffmi::Partials p;
+  p.p = slabs, p.S = S, p.NP = NP;
+  FFMI_HIP(ffmi::launch_rmsnorm((const uint16_t *)x1, nullptr, (const uint16_t *)w,
+                                (uint16_t *)residual_out, (uint16_t *)out, T, H, eps,
+                                (hipStream_t)stream, packed, p));
+  return FFMI_OK;
+}
+
+extern "C" ffmi_status ffmi_debug_attn_partials(ffmi_attn *h, const ffmi_batch_dev *b,
+                                                const float *slabs, int S, int NP, void *out,
+                                                ffmi_stream stream) {
+  FFMI_CHECK(h && b && slabs && out && ((size_t)slabs & 15) == 0, FFMI_ERR_INVALID);
+  FFMI_CHECK(!h->cfg.full_precision, FFMI_ERR_INVALID);
+  FFMI_CHECK(S >= 1 && S <= 8, FFMI_ERR_INVALID);
+  FFMI_CHECK(NP >= 3 * h->cfg.num_heads * h->cfg.head_dim && NP % 4 == 0, FFMI_ERR_INVALID);
+  ffmi::Partials p;
+  p.p = slabs, p.S = S, p.NP = NP;
+  return ffmi::attn_forward(h, b, nullptr, p, out, stream);
+}
+
+// Test hook of the embedding gather folded into layer 0's norm (launch_rmsnorm
+// with `gather`), on the device blob or -- desc given -- as the model's blob
+// fetch: the step staged but not copied, the norm's grid copying it.
+extern "C" ffmi_status ffmi_debug_rmsnorm_gather(ffmi_batch_dev *b, const ffmi_batch_desc *desc,
+                                                 const void *table, const void *w,
+                                                 void *residual_out, void *out, int H, float eps,
+                                                 int flags, const int32_t *prev_ids,
+                                                 ffmi_stream stream) {
+  FFMI_CHECK(b && table && w && residual_out && out, FFMI_ERR_INVALID);
+  FFMI_CHECK(H >= 8 && H % 8 == 0 && H <= 32768, FFMI_ERR_INVALID);
+  FFMI_CHECK((flags & ~FFMI_Y_PACKED) == 0, FFMI_ERR_INVALID);
+  const bool packed = (flags & FFMI_Y_PACKED) != 0;
+  FFMI_CHECK(!packed || H % 32 == 0, FFMI_ERR_UNSUPPORTED);
+  if (desc && !prev_ids)
+    for (int t = 0; t < desc->num_tokens; ++t)
+      FFMI_CHECK(desc->tokens && desc->tokens[t].token_id >= 0, FFMI_ERR_INVALID);
+  const hipStream_t s = (hipStream_t)stream;
+  if (!desc) {
+    if (!prev_ids) {  // the staging still holds the blob of the last upload
+      const ffmi::BatchHeader *hd = reinterpret_cast<const ffmi::BatchHeader *>(b->host);
+      const ffmi_token_info *tk = reinterpret_cast<const ffmi_token_info *>(b->host + hd->off_tokens);
+      for (int t = 0; t < b->num_tokens; ++t) FFMI_CHECK(tk[t].token_id >= 0, FFMI_ERR_INVALID);
+    }
+    FFMI_HIP(ffmi::launch_rmsnorm((const uint16_t *)table, nullptr, (const uint16_t *)w,
+                                  (uint16_t *)residual_out, (uint16_t *)out, b->num_tokens, H, eps,
+                                  s, packed, ffmi::Partials(), b->dev, nullptr, 0, prev_ids));
+    return FFMI_OK;
+  }
+  size_t bytes = 0;
+  const ffmi_status st = ffmi::batch_stage(b, desc, &bytes);
+  if (st != FFMI_OK) return st;
+  FFMI_HIP(ffmi::launch_rmsnorm((const uint16_t *)table, nullptr, (const uint16_t *)w,
+                                (uint16_t *)residual_out, (uint16_t *)out, b->num_tokens, H, eps, s,
+                                packed, ffmi::Partials(), b->host, b->dev, bytes, prev_ids));
+  // the staging is free for the next stage call once the fetch has read it
+  FFMI_HIP(hipEventRecord(b->uploaded, s));
   return FFMI_OK;
 }
 
@@ -1244,6 +1333,19 @@ extern "C" ffmi_status ffmi_allreduce_rmsnorm(ffmi_comm *c, const void *in, int 
   return ffmi::comm_allreduce_norm(c, in, T, H, col0, (const uint16_t *)prev,
                                    (uint16_t *)residual, (const uint16_t *)w, eps, (uint16_t *)out,
                                    (flags & FFMI_Y_PACKED) != 0, two, (hipStream_t)stream);
+}
+
+// Test hook: the all-reduce whose copy-in sums this rank's split-K slabs
+// (comm_allreduce_cols with slabs, as the model's row-parallel GEMMs use it)
+extern "C" ffmi_status ffmi_debug_allreduce_partials(ffmi_comm *c, const float *slabs, int S,
+                                                     int NP, void *out, int rows, int cols,
+                                                     ffmi_stream stream) {
+  FFMI_CHECK(c && slabs && out && S >= 1 && rows >= 0 && cols >= 0, FFMI_ERR_INVALID);
+  FFMI_CHECK(c->nranks > 1 && c->peer && c->peer->attached, FFMI_ERR_INVALID);
+  ffmi::Partials p;
+  p.p = slabs, p.S = S, p.NP = NP;
+  return ffmi::comm_allreduce_cols(c, nullptr, out, rows, cols, cols, 0, FFMI_F16,
+                                   (hipStream_t)stream, &p);
 }
 
 extern "C" long ffmi_debug_gemm_stamps(long long *dst, long max_waves) {

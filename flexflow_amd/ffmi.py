@@ -224,6 +224,17 @@ SIGNATURES = {
                                                  c_int, c_int, c_void_p]),
     "ffmi_debug_fused_norm_linear": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_void_p,
                                              c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "ffmi_debug_partials_reduce": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int,
+                                           c_void_p]),
+    "ffmi_debug_rmsnorm_partials": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                            c_void_p, c_int, c_int, c_float, c_int, c_void_p]),
+    "ffmi_debug_attn_partials": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                         c_void_p]),
+    "ffmi_debug_allreduce_partials": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int,
+                                              c_int, c_void_p]),
+    "ffmi_debug_rmsnorm_gather": (c_int, [c_void_p, ctypes.POINTER(BatchDesc), c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_int, c_float, c_int, c_void_p,
+                                          c_void_p]),
     "ffmi_debug_attn_stamps": (ctypes.c_long, [c_void_p, ctypes.c_long]),
     "ffmi_debug_markers": (ctypes.c_long, [c_void_p, ctypes.c_long]),
 }

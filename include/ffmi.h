@@ -670,6 +670,64 @@ ffmi_status ffmi_debug_fused_norm_linear(const void *residual, const float *ss_i
                                          void *Y, int T, int out_dim, int in_dim, int epilogue,
                                          ffmi_stream stream);
 
+/* Test hooks: the consumers of deferred split-K slabs.  A split-K GEMM whose
+ * consumer can combine leaves its partial sums as fp32 slabs [S][T][NP]
+ * (NP >= the output width: the GEMM's padded tile columns); the value of
+ * element (t, n) is fp16(slab 0 + slab 1 + ... in slab order), rounded once.
+ * The public entry points never pass slabs (the in-library model does); each
+ * hook below is one consumer fed with caller-made slabs: device memory,
+ * 16-byte aligned, columns [width, NP) never read into a result.  Every
+ * argument check is decided before any HIP call.
+ *
+ * ffmi_debug_partials_reduce: the reduce pass, Y[T][N] fp16 row-major.
+ *   FFMI_ERR_INVALID: a null pointer, T < 0, S < 1, S > 16, NP % 16, N > NP,
+ *   N < 1.
+ * ffmi_debug_rmsnorm_partials: ffmi_rmsnorm_ex(x1, x2, ...) with x2 = the
+ *   slabs' value (residual_out may alias x1, as the model calls it).
+ *   FFMI_ERR_INVALID: a null x1 / slabs / w / out, no residual_out, T < 0,
+ *   S < 1, S > 16, S > 8 with H > 1024, H > 8192, H < 8, H % 8, NP < H,
+ *   NP % 4, unknown flags; FFMI_ERR_UNSUPPORTED: FFMI_Y_PACKED with H % 32.
+ * ffmi_debug_attn_partials: ffmi_attn_inc / _spec / _tree (the handle's mode)
+ *   with qkv [T][3 * heads * head_dim] = the slabs' value.
+ *   FFMI_ERR_INVALID: a null pointer, a full-precision handle, S < 1, S > 8,
+ *   NP < 3 * heads * head_dim, NP % 4.
+ * ffmi_debug_allreduce_partials: ffmi_allreduce of this rank's [rows][cols]
+ *   fp16 partial = the slabs' value, over an attached xGMI transport (the
+ *   reduce pass folded into the copy-in).  FFMI_ERR_INVALID: a null pointer,
+ *   S < 1, rows or cols < 0, no attached transport; then the transport's own
+ *   status (FFMI_ERR_UNSUPPORTED: S > 8, NP < cols, NP % 4, cols % 8;
+ *   nothing is launched). */
+ffmi_status ffmi_debug_partials_reduce(const float *slabs, int S, int NP, void *Y, int T, int N,
+                                       ffmi_stream stream);
+ffmi_status ffmi_debug_rmsnorm_partials(const void *x1, const float *slabs, int S, int NP,
+                                        const void *w, void *residual_out, void *out, int T, int H,
+                                        float eps, int flags, ffmi_stream stream);
+ffmi_status ffmi_debug_attn_partials(ffmi_attn *h, const ffmi_batch_dev *b, const float *slabs,
+                                     int S, int NP, void *out, ffmi_stream stream);
+ffmi_status ffmi_debug_allreduce_partials(ffmi_comm *c, const float *slabs, int S, int NP,
+                                          void *out, int rows, int cols, ffmi_stream stream);
+/* Test hook: the embedding lookup folded into layer 0's norm.  Over batch b's
+ * tokens: residual_out[t] = table[id_t] (H halves per row) and out =
+ * RMSNorm(residual_out) * w (flags: FFMI_Y_PACKED), where id_t is the token id,
+ * or prev_ids[i] for a token id -1 - i (a chained beam step: entry i of the
+ * previous step's top-k; prev_ids is device int32 and may be NULL when no id
+ * is negative).  desc == NULL: b as last uploaded, its device blob read.
+ * desc != NULL: desc is staged in b's pinned staging and NOT copied -- the
+ * norm reads the staging and its grid copies the blob into b's device memory
+ * for the step's later kernels (the model's fetch, in place of the H2D copy).
+ * The ids must index the table / prev_ids: the caller's duty (the one id
+ * check below is best effort: with desc == NULL it reads the blob last staged
+ * on b, which is b's device blob only if ffmi_batch_upload or this hook
+ * staged it).
+ * FFMI_ERR_INVALID: a null b / table / w / residual_out / out, H < 8, H % 8,
+ * H > 32768, unknown flags, a negative token id with prev_ids == NULL, what
+ * ffmi_batch_upload refuses of desc; FFMI_ERR_UNSUPPORTED: FFMI_Y_PACKED with
+ * H % 32. */
+ffmi_status ffmi_debug_rmsnorm_gather(ffmi_batch_dev *b, const ffmi_batch_desc *desc,
+                                      const void *table, const void *w, void *residual_out,
+                                      void *out, int H, float eps, int flags,
+                                      const int32_t *prev_ids, ffmi_stream stream);
+
 /* Diagnostics: with FFMI_GEMM_STAMP set in the environment, M-split GEMM
  * launches record per-wave timestamps; copies the last launch's records
  * ({start, prologue done, k-loop done, end} at 100 MHz, HW_ID, XCC_ID) and
@@ -702,7 +760,10 @@ const char *ffmi_last_error(void);
  * (ffmi_sample_topp, ffmi_sampling_counter, ffmi_model_set_sampling) and,
  * later under the same string (nothing that existed changed), its vocab-
  * sharded form: ffmi_vocab_shard_sample_scratch_bytes and
- * ffmi_vocab_shard_sample_topp */
+ * ffmi_vocab_shard_sample_topp; and the test hooks of the split-K slab
+ * consumers and the gather norm: ffmi_debug_partials_reduce,
+ * ffmi_debug_rmsnorm_partials, ffmi_debug_attn_partials,
+ * ffmi_debug_allreduce_partials, ffmi_debug_rmsnorm_gather */
 const char *ffmi_version(void);
 
 #ifdef __cplusplus

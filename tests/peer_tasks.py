@@ -74,6 +74,44 @@ def arnorm_task(fa, comm, rank, n, cases, seed, iters=2):
     return out
 
 
+def slab_case_data(ci, S, rank, rows, cols, NP):
+    """rank `rank`'s split-K slabs [S][rows][NP] of case ci (tests/partials_rule.py)"""
+    from partials_rule import make_slabs
+    return make_slabs(S, rows, NP, cols, np.random.default_rng([ci, S, rank]))
+
+
+def slab_ar_task(fa, comm, rank, n, cases, Ss, bad_S):
+    """ffmi_debug_allreduce_partials (the all-reduce whose copy-in sums this
+    rank's split-K slabs, slab_vec) per case (rows, cols, NP) and S, and
+    ffmi_allreduce of the fp16 partial combine(slabs) beside it; then the
+    status of a call with bad_S slabs (refused on the host: no rank launches,
+    so the ranks stay in step)."""
+    import flexflow_amd.ffmi as F
+    from hip_util import Buf, sync
+    from partials_rule import combine
+    L = F.lib()
+    out = {}
+    for ci, (rows, cols, NP) in enumerate(cases):
+        for S in Ss:
+            slabs = slab_case_data(ci, S, rank, rows, cols, NP)
+            part = np.ascontiguousarray(combine(slabs)[:, :cols])
+            sb, pb = Buf(slabs), Buf(part)
+            a, b = Buf.empty((rows, cols), np.float16), Buf.empty((rows, cols), np.float16)
+            F.check(L.ffmi_debug_allreduce_partials(comm.handle, sb.ptr, S, NP, a.ptr, rows, cols,
+                                                    None), "allreduce_partials")
+            F.check(L.ffmi_allreduce(comm.handle, pb.ptr, b.ptr, rows * cols, F.F16, None),
+                    "allreduce")
+            sync()
+            out[(ci, S)] = (a.get(), b.get())
+    rows, cols, NP = cases[0]
+    sb, a = Buf(slab_case_data(0, bad_S, rank, rows, cols, NP)), Buf.empty((rows, cols), np.float16)
+    out["bad_S"] = int(L.ffmi_debug_allreduce_partials(comm.handle, sb.ptr, bad_S, NP, a.ptr, rows,
+                                                       cols, None))
+    sync()
+    out["bad_S_out"] = a.get()
+    return out
+
+
 def expected_sum(case, it, n, count, dtype):
     acc = np.zeros(count, np.float32)
     for r in range(n):  # rank order, fp32, rounded once

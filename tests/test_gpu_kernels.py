@@ -637,6 +637,8 @@ class AttnCase:
                         1.0 / np.sqrt(d), theta, out_layout, *l3, int(fp32))
         self.h = ctypes.c_void_p()
         F.check(L.ffmi_attn_create(ctypes.byref(cfg), ctypes.byref(self.h)))
+        self.cfg, self.twin = cfg, None  # (twin: run's slabs option)
+        self.max_requests = max_requests
         self.b = ctypes.c_void_p()
         F.check(L.ffmi_batch_create(max_tokens, max_requests, ctypes.byref(self.b)))
         slots = ctypes.c_int()
@@ -654,11 +656,35 @@ class AttnCase:
         out = np.concatenate([a * c - b * s, a * s + b * c], axis=1)
         return out if self.fp32 else f16(out).astype(np.float32)
 
-    def run(self, infos, masks=None, commits=(), rng=None):
+    def caches(self, h):
+        """the K and V^T caches of handle h (ffmi_attn_kv_ptrs), as bits"""
+        k, v = ctypes.c_void_p(), ctypes.c_void_p()
+        F.check(L.ffmi_attn_kv_ptrs(h, ctypes.byref(k), ctypes.byref(v), None))
+        n = self.max_requests * self.heads * self.slots * self.d
+        kc, vc = np.empty(n, np.uint16), np.empty(n, np.uint16)
+        assert hip().hipDeviceSynchronize() == 0
+        assert hip().hipMemcpy(kc.ctypes.data, k, n * 2, 2) == 0
+        assert hip().hipMemcpy(vc.ctypes.data, v, n * 2, 2) == 0
+        return kc, vc
+
+    def run(self, infos, masks=None, commits=(), rng=None, slabs=None, slab_pad=0):
+        """slabs = S: the step's qkv arrives as S deferred split-K slabs
+        (partials_rule.make_slabs, [S][T][3 * Hl + slab_pad] fp32) through
+        ffmi_debug_attn_partials; a twin handle takes the same batch through
+        ffmi_attn_* with qkv = combine(slabs), and its output, K cache and
+        V^T cache must equal this handle's bit for bit after the step (fp16
+        handles).  The oracle side sees the combined qkv."""
         T = len(infos)
-        qkv = rng.standard_normal((T, 3 * self.Hl)).astype(np.float32)
-        if not self.fp32:
-            qkv = f16(qkv)
+        if slabs:
+            from partials_rule import combine, make_slabs
+            assert not self.fp32 and slab_pad % 4 == 0
+            N = 3 * self.Hl
+            sl = make_slabs(slabs, T, N + slab_pad, N, rng)
+            qkv = np.ascontiguousarray(combine(sl)[:, :N])
+        else:
+            qkv = rng.standard_normal((T, 3 * self.Hl)).astype(np.float32)
+            if not self.fp32:
+                qkv = f16(qkv)
         self.last_qkv = qkv  # the step's inputs, for tests that read the caches back
         # tree_vis is derived by ffmi_batch_upload from masks/tree_bit
         toks = (F.TokenInfo * T)(*[F.TokenInfo(*i, 0) for i in infos])
@@ -688,7 +714,19 @@ class AttnCase:
         qb, ob = Buf(qkv), Buf.empty((Tp, self.Hl), np.float32 if self.fp32 else np.float16)
         fn = {F.ATTN_INC: L.ffmi_attn_inc, F.ATTN_SPEC: L.ffmi_attn_spec,
               F.ATTN_TREE: L.ffmi_attn_tree}[self.mode]
-        F.check(fn(self.h, self.b, qb.ptr, ob.ptr, None))
+        if slabs:
+            if self.twin is None:
+                self.twin = ctypes.c_void_p()
+                F.check(L.ffmi_attn_create(ctypes.byref(self.cfg), ctypes.byref(self.twin)))
+            sb, tb = Buf(sl), Buf.empty((Tp, self.Hl), np.float16)
+            F.check(L.ffmi_debug_attn_partials(self.h, self.b, sb.ptr, slabs, N + slab_pad, ob.ptr,
+                                               None))
+            F.check(fn(self.twin, self.b, qb.ptr, tb.ptr, None))
+            assert np.array_equal(ob.get().view(np.uint16), tb.get().view(np.uint16)), "slab out"
+            for name, a, b in zip(("K", "V^T"), self.caches(self.h), self.caches(self.twin)):
+                assert np.array_equal(a, b), f"slab {name} cache"
+        else:
+            F.check(fn(self.h, self.b, qb.ptr, ob.ptr, None))
         out = ob.get()
         out = unpack_act_np(out.reshape(-1), T, self.Hl) if self.out_layout else out[:T]
         # oracle side: commits, stores, then attention rows
@@ -1056,21 +1094,22 @@ def test_attention_spec_beam_layers(fp32):
     _spec_beam_layers(AttnCase(F.ATTN_SPEC, d=64, fp32=fp32), 8, np.random.default_rng(7))
 
 
-def _spec_beam_layers(c, ntcs, rng):
-    """beam layers over a prompt of ntcs + 1 tokens (root = the last one)"""
+def _spec_beam_layers(c, ntcs, rng, **run_kw):
+    """beam layers over a prompt of ntcs + 1 tokens (root = the last one);
+    run_kw: further arguments of every AttnCase.run call (slabs)"""
     infos = [(3, p, 0, p, p + 1, 0, 0, 0) for p in range(ntcs + 1)]
-    c.run(infos, masks=[[0]], rng=rng)
+    c.run(infos, masks=[[0]], rng=rng, **run_kw)
     # tree so far: root(idx0 @ slot ntcs) -> n1 (idx1) -> {n2, n3} (idx 2,3);
     # this step's layer: n4 (child of n2), n5 (child of n3) at tree idx 4,5
     parents = [-1, 0, 1, 1, 2, 3]
     m = tree_masks(parents)
     # earlier layers were stored by previous steps: emulate with one step
     infos = [(5, ntcs + 1, 0, ntcs + 1, ntcs, ntcs, 2, 1)]
-    c.run(infos, masks=[m], rng=rng)
+    c.run(infos, masks=[m], rng=rng, **run_kw)
     infos = [(5, ntcs + 2, 0, ntcs + 2 + k, ntcs, ntcs, 4, 2 + k) for k in range(2)]
-    c.run(infos, masks=[m], rng=rng)
+    c.run(infos, masks=[m], rng=rng, **run_kw)
     infos = [(6, ntcs + 3, 0, ntcs + 4 + k, ntcs, ntcs, 6, 4 + k) for k in range(2)]
-    out, qs = c.run(infos, masks=[m], rng=rng)
+    out, qs = c.run(infos, masks=[m], rng=rng, **run_kw)
     for k in range(2):
         j = 4 + k
         anc = []

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import peer_tasks as PT
+from partials_rule import PEER_CASES
 from peer_group import run_group
 
 pytestmark = pytest.mark.gpu
@@ -35,6 +36,44 @@ def test_peer_allreduce_exact(n, two_shot):
                 got = res[r][(it, ci)]
                 assert got.dtype == want.dtype
                 np.testing.assert_array_equal(got, want, err_msg=f"rank {r} case {ci} round {it}")
+
+
+# (rows, cols, NP): one 16-byte vector in all; a padded slab width with rows
+# that are no multiple of the workgroup; a tile of padding
+# (the list lives in partials_rule, where the CPU order-sensitivity test reads it)
+SLAB_CASES = list(PEER_CASES)
+assert SLAB_CASES == [(1, 8, 16), (5, 1000, 1008), (33, 1024, 1040)]
+SLAB_S = (1, 2, 3, 4, 5, 8)
+
+
+@pytest.mark.parametrize("n,two_shot", [(2, False), (2, True), (4, False), (4, True)])
+def test_peer_allreduce_slab_copy_in_exact(n, two_shot):
+    """The all-reduce whose copy-in sums the rank's deferred split-K slabs
+    (slab_vec<2 / 4 / 8>, one- and two-shot): on every rank bit-identical to
+    ffmi_allreduce of the fp16 partial combine(slabs) (tests/partials_rule.py:
+    slab order, rounded once; cancelling pairs, NaN padding columns), and to
+    the numpy sum of those partials in rank order, rounded once.  9 slabs are
+    refused as unsupported on every rank, with nothing launched (the output
+    buffer stays zero and the ranks stay in step)."""
+    from partials_rule import combine
+    env = {"FFMI_PEER_TWO_SHOT_MIN": "0" if two_shot else str(1 << 40)}
+    res = run_group(n, PT.slab_ar_task, (SLAB_CASES, SLAB_S, 9), env=env, max_bytes=1 << 20)
+    for ci, (rows, cols, NP) in enumerate(SLAB_CASES):
+        for S in SLAB_S:
+            acc = np.zeros((rows, cols), np.float32)
+            for r in range(n):  # rank order, fp32, rounded once
+                part = combine(PT.slab_case_data(ci, S, r, rows, cols, NP))[:, :cols]
+                acc = acc + part.astype(np.float32)
+            want = acc.astype(np.float16).view(np.uint16)
+            for r in range(n):
+                slab_out, plain_out = res[r][(ci, S)]
+                ctx = f"rank {r} case {ci} S {S}"
+                np.testing.assert_array_equal(slab_out.view(np.uint16), plain_out.view(np.uint16),
+                                              err_msg=ctx)
+                np.testing.assert_array_equal(slab_out.view(np.uint16), want, err_msg=ctx)
+    for r in range(n):
+        assert res[r]["bad_S"] == 5, r  # FFMI_ERR_UNSUPPORTED
+        assert not res[r]["bad_S_out"].view(np.uint16).any(), r
 
 
 def test_peer_allreduce_silent_peer_times_out():
