@@ -49,7 +49,8 @@ extern "C" const char *ffmi_status_str(ffmi_status s) {
 // 0.4: top-p sampling (ffmi_sample_topp, ffmi_sampling_counter, ffmi_model_set_sampling);
 // then, with no change to anything there before (the string stays), its
 // vocab-sharded form: ffmi_vocab_shard_sample_scratch_bytes, ffmi_vocab_shard_sample_topp,
-// and the ffmi_debug_*_partials / ffmi_debug_rmsnorm_gather test hooks
+// and the ffmi_debug_*_partials / ffmi_debug_rmsnorm_gather / ffmi_debug_attn_oproj
+// test hooks
 extern "C" const char *ffmi_version(void) { return "ffmi 0.4 (gfx950)"; }
 
 // ---------------------------------------------------------------------------
@@ -241,7 +242,7 @@ extern "C" ffmi_status ffmi_batch_upload(ffmi_batch_dev *b, const ffmi_batch_des
 // attention handles
 // ---------------------------------------------------------------------------
 struct ffmi_attn {
-  ffmi_attn_cfg cfg;  // first: all ffmi_debug_attn_partials reads before it refuses
+  ffmi_attn_cfg cfg;  // first: all ffmi_debug_attn_partials / _oproj read before they refuse
                       // (tests/test_partials_cpu.py fabricates that much without a device)
   int slots = 0;
   uint16_t *kc = nullptr, *vc = nullptr, *qbuf = nullptr, *stage = nullptr;
@@ -723,6 +724,35 @@ extern "C" ffmi_status ffmi_debug_attn_partials(ffmi_attn *h, const ffmi_batch_d
   ffmi::Partials p;
   p.p = slabs, p.S = S, p.NP = NP;
   return ffmi::attn_forward(h, b, nullptr, p, out, stream);
+}
+
+// Test hook of the output projection folded into the fused attention
+// (ffmi::OprojArgs, filled as llama_gpu.cpp fills it): the handle's mode
+// through attn_forward, qkv as fp16 rows or as slabs.  An ineligible launch
+// geometry is attn_forward's decision, not an error: *projected = 0.
+extern "C" ffmi_status ffmi_debug_attn_oproj(ffmi_attn *h, const ffmi_batch_dev *b,
+                                             const void *qkv, const float *qkv_slabs, int S,
+                                             int NP, void *out, const void *Wo_packed, int N,
+                                             float *slab, int max_T, int *projected,
+                                             ffmi_stream stream) {
+  FFMI_CHECK(h && b && out && Wo_packed && slab && projected, FFMI_ERR_INVALID);
+  FFMI_CHECK((qkv != nullptr) != (qkv_slabs != nullptr), FFMI_ERR_INVALID);
+  FFMI_CHECK(!h->cfg.full_precision && h->cfg.head_dim == 64, FFMI_ERR_INVALID);
+  FFMI_CHECK(N >= 16 && N % 16 == 0 && N <= 1024 && max_T >= 1, FFMI_ERR_INVALID);
+  FFMI_CHECK(((size_t)slab & 15) == 0, FFMI_ERR_INVALID);
+  ffmi::Partials p;
+  if (qkv_slabs) {
+    FFMI_CHECK(((size_t)qkv_slabs & 15) == 0 && S >= 1 && S <= 8, FFMI_ERR_INVALID);
+    FFMI_CHECK(NP >= 3 * h->cfg.num_heads * h->cfg.head_dim && NP % 4 == 0, FFMI_ERR_INVALID);
+    p.p = qkv_slabs, p.S = S, p.NP = NP;
+  }
+  const int Hl = h->cfg.num_heads * h->cfg.head_dim;
+  ffmi::OprojArgs oa;
+  oa.wo = (const uint16_t *)Wo_packed, oa.slab = slab, oa.N = N, oa.max_T = max_T;
+  oa.wts = ffmi::w_tile_stride(Hl / 32), oa.wks = ffmi::w_k_stride(N / 16);
+  const ffmi_status st = ffmi::attn_forward(h, b, qkv, p, out, stream, -1, &oa);
+  *projected = oa.done ? 1 : 0;
+  return st;
 }
 
 // Test hook of the embedding gather folded into layer 0's norm (launch_rmsnorm

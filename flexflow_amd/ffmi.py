@@ -235,6 +235,9 @@ SIGNATURES = {
     "ffmi_debug_rmsnorm_gather": (c_int, [c_void_p, ctypes.POINTER(BatchDesc), c_void_p, c_void_p,
                                           c_void_p, c_void_p, c_int, c_float, c_int, c_void_p,
                                           c_void_p]),
+    "ffmi_debug_attn_oproj": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                      c_void_p, c_int, c_void_p, c_int, ctypes.POINTER(c_int),
+                                      c_void_p]),
     "ffmi_debug_attn_stamps": (ctypes.c_long, [c_void_p, ctypes.c_long]),
     "ffmi_debug_markers": (ctypes.c_long, [c_void_p, ctypes.c_long]),
 }

@@ -727,6 +727,32 @@ ffmi_status ffmi_debug_rmsnorm_gather(ffmi_batch_dev *b, const ffmi_batch_desc *
                                       const void *table, const void *w, void *residual_out,
                                       void *out, int H, float eps, int flags,
                                       const int32_t *prev_ids, ffmi_stream stream);
+/* Test hook: the output projection folded into the fused attention (small
+ * models: head_dim 64, N <= 1024 output columns).  Runs ffmi_attn_inc / _spec
+ * / _tree (the handle's mode) on batch b with qkv [T][3 * heads * 64] fp16 --
+ * or, qkv == NULL, with the step's qkv as slabs [S][T][NP] under the rules of
+ * ffmi_debug_attn_partials; exactly one of the two is given -- and asks the
+ * launch to multiply each head's rounded fp16 output rows by that head's 64
+ * columns of Wo_packed = ffmi_linear_pack_weight(Wo, N, heads * 64):
+ *   slab[h][t][n] = sum_k out[t][h * 64 + k] * Wo[n][h * 64 + k]   (fp32)
+ * for the T tokens of b, slab = [heads][T][N] with row stride T, not max_T
+ * (max_T: the rows the caller's buffer holds per head).  The projection sums
+ * slab over h in order and rounds once (ffmi_debug_rmsnorm_partials with
+ * S = heads, NP = N).  *projected = 1.
+ * An ineligible launch geometry is not an error: where the step is not one
+ * work item per request, does not fit the fused kernel's LDS tail, has an
+ * item of more than 16 queries or more than max_T tokens, or with
+ * FFMI_ATTN_NO_FUSE set, the attention runs as usual, *projected = 0 and slab
+ * is not touched (the caller runs the GEMM).  Every argument check is decided
+ * before any HIP call.
+ * FFMI_ERR_INVALID: a null h / b / out / Wo_packed / slab / projected, both
+ * or neither of qkv and qkv_slabs, a full-precision handle, head_dim != 64,
+ * N < 16, N % 16, N > 1024, max_T < 1, a slab not 16-byte aligned; with
+ * qkv_slabs: not 16-byte aligned, S < 1, S > 8, NP < 3 * heads * 64, NP % 4. */
+ffmi_status ffmi_debug_attn_oproj(ffmi_attn *h, const ffmi_batch_dev *b, const void *qkv,
+                                  const float *qkv_slabs, int S, int NP, void *out,
+                                  const void *Wo_packed, int N, float *slab, int max_T,
+                                  int *projected, ffmi_stream stream);
 
 /* Diagnostics: with FFMI_GEMM_STAMP set in the environment, M-split GEMM
  * launches record per-wave timestamps; copies the last launch's records
@@ -763,7 +789,8 @@ const char *ffmi_last_error(void);
  * ffmi_vocab_shard_sample_topp; and the test hooks of the split-K slab
  * consumers and the gather norm: ffmi_debug_partials_reduce,
  * ffmi_debug_rmsnorm_partials, ffmi_debug_attn_partials,
- * ffmi_debug_allreduce_partials, ffmi_debug_rmsnorm_gather */
+ * ffmi_debug_allreduce_partials, ffmi_debug_rmsnorm_gather; and of the
+ * output projection folded into the fused attention: ffmi_debug_attn_oproj */
 const char *ffmi_version(void);
 
 #ifdef __cplusplus

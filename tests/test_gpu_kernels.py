@@ -667,21 +667,36 @@ class AttnCase:
         assert hip().hipMemcpy(vc.ctypes.data, v, n * 2, 2) == 0
         return kc, vc
 
-    def run(self, infos, masks=None, commits=(), rng=None, slabs=None, slab_pad=0):
+    def run(self, infos, masks=None, commits=(), rng=None, slabs=None, slab_pad=0, oproj=None,
+            qkv=None):
         """slabs = S: the step's qkv arrives as S deferred split-K slabs
         (partials_rule.make_slabs, [S][T][3 * Hl + slab_pad] fp32) through
         ffmi_debug_attn_partials; a twin handle takes the same batch through
         ffmi_attn_* with qkv = combine(slabs), and its output, K cache and
         V^T cache must equal this handle's bit for bit after the step (fp16
-        handles).  The oracle side sees the combined qkv."""
+        handles).  The oracle side sees the combined qkv.
+
+        oproj = (Wo fp16 [N][Hl], N, max_T): the step goes through
+        ffmi_debug_attn_oproj (with qkv, or with the slabs above), which asks
+        the launch to project each head's output rows into a slab buffer
+        (oproj_rule.slab_buffer: sentinel words, heads * max_T * N between two
+        guards).  The twin comparison above is made as well -- the projection
+        must not disturb the attention -- and every word of the buffer outside
+        [heads][T][N] (all of it when the launch did not project) must still
+        hold the sentinel.  Returns (out, qs, slab, projected), slab float32
+        [heads][T][N] or None.
+
+        qkv: the step's qkv rows, given instead of drawn."""
         T = len(infos)
-        if slabs:
+        if qkv is not None:
+            assert not slabs and qkv.shape == (T, 3 * self.Hl)
+        elif slabs:
             from partials_rule import combine, make_slabs
             assert not self.fp32 and slab_pad % 4 == 0
             N = 3 * self.Hl
             sl = make_slabs(slabs, T, N + slab_pad, N, rng)
             qkv = np.ascontiguousarray(combine(sl)[:, :N])
-        else:
+        elif qkv is None:
             qkv = rng.standard_normal((T, 3 * self.Hl)).astype(np.float32)
             if not self.fp32:
                 qkv = f16(qkv)
@@ -714,13 +729,25 @@ class AttnCase:
         qb, ob = Buf(qkv), Buf.empty((Tp, self.Hl), np.float32 if self.fp32 else np.float16)
         fn = {F.ATTN_INC: L.ffmi_attn_inc, F.ATTN_SPEC: L.ffmi_attn_spec,
               F.ATTN_TREE: L.ffmi_attn_tree}[self.mode]
-        if slabs:
+        if slabs or oproj:
             if self.twin is None:
                 self.twin = ctypes.c_void_p()
                 F.check(L.ffmi_attn_create(ctypes.byref(self.cfg), ctypes.byref(self.twin)))
-            sb, tb = Buf(sl), Buf.empty((Tp, self.Hl), np.float16)
-            F.check(L.ffmi_debug_attn_partials(self.h, self.b, sb.ptr, slabs, N + slab_pad, ob.ptr,
-                                               None))
+            sb, tb = Buf(sl) if slabs else None, Buf.empty((Tp, self.Hl), np.float16)
+            if oproj:
+                import oproj_rule as R
+                Wo, No, max_T = oproj
+                assert not self.fp32 and Wo.dtype == np.float16 and Wo.shape == (No, self.Hl)
+                wp, pj = packed(Wo), ctypes.c_int(-1)
+                zb = Buf(R.slab_buffer(self.heads, max_T, No))
+                F.check(L.ffmi_debug_attn_oproj(
+                    self.h, self.b, None if slabs else qb.ptr, sb.ptr if slabs else None,
+                    slabs or 0, N + slab_pad if slabs else 0, ob.ptr, wp.ptr, No,
+                    ctypes.c_void_p(zb.ptr.value + 4 * R.GUARD), max_T, ctypes.byref(pj), None))
+                assert pj.value in (0, 1)
+            else:
+                F.check(L.ffmi_debug_attn_partials(self.h, self.b, sb.ptr, slabs, N + slab_pad,
+                                                   ob.ptr, None))
             F.check(fn(self.twin, self.b, qb.ptr, tb.ptr, None))
             assert np.array_equal(ob.get().view(np.uint16), tb.get().view(np.uint16)), "slab out"
             for name, a, b in zip(("K", "V^T"), self.caches(self.h), self.caches(self.twin)):
@@ -744,6 +771,8 @@ class AttnCase:
                 self.kc[(i[2], i[3])] = (k, v)
             qs.append(q)
         self.prev_stage = stage
+        if oproj:
+            return out, qs, R.split_buffer(zb.get(), self.heads, T, No, pj.value == 1), pj.value
         return out, qs
 
     def ref_row(self, q, req, visible_slots):

@@ -155,7 +155,7 @@ def test_rmsnorm_gather_refusals():
 
 @pytest.mark.parametrize("name", ["ffmi_debug_partials_reduce", "ffmi_debug_rmsnorm_partials",
                                   "ffmi_debug_attn_partials", "ffmi_debug_allreduce_partials",
-                                  "ffmi_debug_rmsnorm_gather"])
+                                  "ffmi_debug_rmsnorm_gather", "ffmi_debug_attn_oproj"])
 def test_hooks_are_declared_bound_and_exported(name):
     import os
     import re
