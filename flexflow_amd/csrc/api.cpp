@@ -50,7 +50,10 @@ extern "C" const char *ffmi_status_str(ffmi_status s) {
 // then, with no change to anything there before (the string stays), its
 // vocab-sharded form: ffmi_vocab_shard_sample_scratch_bytes, ffmi_vocab_shard_sample_topp,
 // and the ffmi_debug_*_partials / ffmi_debug_rmsnorm_gather / ffmi_debug_attn_oproj
-// test hooks
+// test hooks;
+// then native grouped-query attention, again by addition only:
+// ffmi_attn_create_gqa, ffmi_attn_cache_bytes, ffmi_attn_set_gqa_route,
+// ffmi_model_create_ex (FFMI_MODEL_NATIVE_GQA), ffmi_model_kv_cache_bytes
 extern "C" const char *ffmi_version(void) { return "ffmi 0.4 (gfx950)"; }
 
 // ---------------------------------------------------------------------------
@@ -248,6 +251,10 @@ struct ffmi_attn {
   uint16_t *kc = nullptr, *vc = nullptr, *qbuf = nullptr, *stage = nullptr;
   int parity = 0;  // TREE staging half written by the next public-API step
   float *rope = nullptr;
+  // GQA (ffmi_attn_create_gqa): K/V heads of the caches and the staging rows
+  // (== cfg.num_heads: MHA, every launch as before), and the route hook
+  int kv_heads = 0;
+  int gqa_route = 0;  // 0 auto, 1 kv-indexed, 2 group-shared where eligible
 };
 static_assert(offsetof(ffmi_attn, cfg) == 0, "ffmi_attn starts with its cfg (test_partials_cpu.py)");
 
@@ -288,7 +295,7 @@ static void rope_table(std::vector<float> &tab, int max_pos, int d, const ffmi_a
     }
 }
 
-extern "C" ffmi_status ffmi_attn_create(const ffmi_attn_cfg *cfg, ffmi_attn **out) {
+static ffmi_status attn_create(const ffmi_attn_cfg *cfg, int kv_heads, ffmi_attn **out) {
   FFMI_CHECK(cfg && out, FFMI_ERR_INVALID);
   // head sizes of the reference's kernels: 32 / 64 / 128 for incremental
   // decoding (inc_multihead_self_attention.cu:911-926), 64 / 128 for tree
@@ -304,9 +311,11 @@ extern "C" ffmi_status ffmi_attn_create(const ffmi_attn_cfg *cfg, ffmi_attn **ou
              FFMI_ERR_UNSUPPORTED);
   ffmi_attn *h = new ffmi_attn();
   h->cfg = *cfg;
+  h->kv_heads = kv_heads;
   h->slots = (cfg->max_seq_len + cfg->max_tree_tokens + 31) & ~31;
   const size_t Hl = (size_t)cfg->num_heads * cfg->head_dim;
-  const size_t kv = (size_t)cfg->max_requests * cfg->num_heads * h->slots * cfg->head_dim;
+  const size_t Hkv = (size_t)kv_heads * cfg->head_dim;  // (== Hl for MHA)
+  const size_t kv = (size_t)cfg->max_requests * kv_heads * h->slots * cfg->head_dim;
   // element size: fp16, or fp32 for DT_FLOAT (the fp32 kernels stage one
   // TREE batch: their commits run before the step's stores, no ping-pong)
   const bool f32 = cfg->full_precision != 0;
@@ -321,7 +330,7 @@ extern "C" ffmi_status ffmi_attn_create(const ffmi_attn_cfg *cfg, ffmi_attn **ou
             hipMalloc((void **)&h->vc, kv * es) == hipSuccess &&
             hipMalloc((void **)&h->qbuf, (size_t)cfg->max_tokens * Hl * es) == hipSuccess;
   if (ok && cfg->mode == FFMI_ATTN_TREE)
-    ok = hipMalloc((void **)&h->stage, (size_t)cfg->max_tokens * 2 * Hl * es * stage_halves) ==
+    ok = hipMalloc((void **)&h->stage, (size_t)cfg->max_tokens * 2 * Hkv * es * stage_halves) ==
          hipSuccess;
   std::vector<float> tab;
   rope_table(tab, h->slots, cfg->head_dim, cfg);
@@ -336,9 +345,46 @@ extern "C" ffmi_status ffmi_attn_create(const ffmi_attn_cfg *cfg, ffmi_attn **ou
   FFMI_HIP(hipMemset(h->kc, 0, kv * es));
   FFMI_HIP(hipMemset(h->vc, 0, kv * es));
   if (h->stage)
-    FFMI_HIP(hipMemset(h->stage, 0, (size_t)cfg->max_tokens * 2 * Hl * es * stage_halves));
+    FFMI_HIP(hipMemset(h->stage, 0, (size_t)cfg->max_tokens * 2 * Hkv * es * stage_halves));
   FFMI_HIP(hipMemcpy(h->rope, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
   *out = h;
+  return FFMI_OK;
+}
+
+extern "C" ffmi_status ffmi_attn_create(const ffmi_attn_cfg *cfg, ffmi_attn **out) {
+  FFMI_CHECK(cfg && out, FFMI_ERR_INVALID);
+  return attn_create(cfg, cfg->num_heads, out);
+}
+
+// Native grouped-query attention: query head h attends K/V head h / G, G =
+// num_heads / num_kv_heads (HF repeat_kv), over caches of num_kv_heads heads.
+// fp16, head_dim 64 / 128.  The refusals below precede every HIP call.
+extern "C" ffmi_status ffmi_attn_create_gqa(const ffmi_attn_cfg *cfg, int num_kv_heads,
+                                            ffmi_attn **out) {
+  FFMI_CHECK(cfg && out, FFMI_ERR_INVALID);
+  if (num_kv_heads <= 0 || num_kv_heads == cfg->num_heads) return ffmi_attn_create(cfg, out);
+  FFMI_CHECK(cfg->num_heads > 0 && cfg->num_heads % num_kv_heads == 0, FFMI_ERR_INVALID);
+  if (cfg->full_precision) {
+    ffmi_set_last_error("native gqa: fp16 only (full_precision handles replicate K/V)", __FILE__,
+                        __LINE__);
+    return FFMI_ERR_UNSUPPORTED;
+  }
+  if (cfg->head_dim != 64 && cfg->head_dim != 128) {
+    ffmi_set_last_error("native gqa: head_dim 64 or 128", __FILE__, __LINE__);
+    return FFMI_ERR_UNSUPPORTED;
+  }
+  return attn_create(cfg, num_kv_heads, out);
+}
+
+extern "C" size_t ffmi_attn_cache_bytes(ffmi_attn *h) {
+  if (!h) return 0;
+  return (size_t)2 * h->cfg.max_requests * h->kv_heads * h->slots * h->cfg.head_dim *
+         (h->cfg.full_precision ? 4 : 2);
+}
+
+extern "C" ffmi_status ffmi_attn_set_gqa_route(ffmi_attn *h, int route) {
+  FFMI_CHECK(h && route >= 0 && route <= 2, FFMI_ERR_INVALID);
+  h->gqa_route = route;
   return FFMI_OK;
 }
 
@@ -388,6 +434,11 @@ ffmi_status attn_forward(ffmi_attn *h, const ffmi_batch_dev *b, const void *qkv,
   const bool tree = h->cfg.mode == FFMI_ATTN_TREE;
   const hipStream_t s = (hipStream_t)stream;
   const int heads = h->cfg.num_heads, d = h->cfg.head_dim;
+  const int kvh = h->kv_heads > 0 ? h->kv_heads : heads, gq = heads / kvh;
+  if (gq > 1 && qkvp.S > 0) {  // (routed around: the model materialises fp16 qkv)
+    ffmi_set_last_error("native gqa: qkv as fp16 rows, not split-K slabs", __FILE__, __LINE__);
+    return FFMI_ERR_UNSUPPORTED;
+  }
   if (h->cfg.full_precision) {
     // DT_FLOAT: commits (TREE), then RoPE + KV store (+ staging), then the
     // attention, each its own launch (kernels/f32.hip)
@@ -405,7 +456,7 @@ ffmi_status attn_forward(ffmi_attn *h, const ffmi_batch_dev *b, const void *qkv,
   int C = 0;
   if (tree) {
     if (parity < 0) parity = h->parity, h->parity ^= 1;
-    const size_t half = (size_t)h->cfg.max_tokens * 2 * heads * d;
+    const size_t half = (size_t)h->cfg.max_tokens * 2 * kvh * d;
     stage_wr = h->stage + (parity ? half : 0);
     stage_rd = h->stage + (parity ? 0 : half);
     C = b->num_commits;
@@ -417,26 +468,36 @@ ffmi_status attn_forward(ffmi_attn *h, const ffmi_batch_dev *b, const void *qkv,
   // commit-then-store order).  FFMI_ATTN_NO_FUSE=1 forces the two-launch path
   // (A/B and parity tests).
   const bool no_fuse = getenv("FFMI_ATTN_NO_FUSE") != nullptr;
-  const bool fused = b->one_item_per_req && b->lds_tail && !no_fuse;
+  // (Such a step takes the two-launch path: the fused prologue's LDS tail
+  // holds the slots the step's own commits and stores write, and would miss
+  // the ones only the separate commit launch wrote.)
+  const bool fused = b->one_item_per_req && b->lds_tail && !no_fuse &&
+                     !(C > 0 && b->commit_overlap);
   if (C > 0 && b->commit_overlap) {
-    FFMI_HIP(ffmi::launch_commit(b->dev, C, stage_rd, h->kc, h->vc, heads, d, h->slots, s));
+    // (per K/V head: the staging rows and the caches hold kvh of them)
+    FFMI_HIP(ffmi::launch_commit(b->dev, C, stage_rd, h->kc, h->vc, kvh, d, h->slots, s));
     C = 0;
   }
   if (!fused) {
     FFMI_HIP(ffmi::launch_kv_update(b->dev, b->num_tokens, b->num_work, C,
                                     (const uint16_t *)qkv, qkvp, h->qbuf, h->kc, h->vc, stage_wr,
-                                    stage_rd, h->rope, heads, d, h->slots, h->slots, s));
+                                    stage_rd, h->rope, heads, d, h->slots, h->slots, s, kvh));
     C = 0;
   }
+  // GQA: the group-shared form (one workgroup per item and K/V head, the
+  // group's query heads as rows of its tile) where every item's queries x
+  // group fit the 16 rows; route 1 keeps the kv-indexed forms (tests, A/B)
+  const bool gqa_shared = gq > 1 && h->gqa_route != 1 && b->max_q * gq <= 16;
   // the output projection rides along where its launch allows it (fused,
   // one query tile, d = 64, N <= 1024 columns); otherwise the caller runs it
-  const bool oproj = opa && opa->wo && opa->slab && fused && d == 64 && b->max_q <= 16 &&
-                     opa->N % 16 == 0 && opa->N <= 1024 && b->num_tokens <= opa->max_T;
+  const bool oproj = opa && opa->wo && opa->slab && gq == 1 && fused && d == 64 &&
+                     b->max_q <= 16 && opa->N % 16 == 0 && opa->N <= 1024 &&
+                     b->num_tokens <= opa->max_T;
   FFMI_HIP(ffmi::launch_attention(b->dev, b->num_work, b->max_q, h->qbuf, h->kc, h->vc,
                                   (uint16_t *)out, heads, d, h->slots, h->cfg.qk_scale, s,
                                   h->cfg.out_layout == 1, fused, b->num_tokens, C,
                                   (const uint16_t *)qkv, qkvp, stage_wr, stage_rd, h->rope,
-                                  h->slots, oproj ? opa : nullptr));
+                                  h->slots, oproj ? opa : nullptr, kvh, gqa_shared));
   if (oproj) opa->done = true;
   return FFMI_OK;
 }

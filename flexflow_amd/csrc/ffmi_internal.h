@@ -279,7 +279,8 @@ size_t vshard_sample_state_bytes(int T);
 hipError_t launch_kv_update(const char *blob, int T, int W, int C, const uint16_t *qkv,
                             Partials qkvp, uint16_t *qbuf, uint16_t *kc, uint16_t *vc,
                             uint16_t *stage_wr, const uint16_t *stage_rd, const float *rope,
-                            int heads, int d, int slots, int max_rope_pos, hipStream_t s);
+                            int heads, int d, int slots, int max_rope_pos, hipStream_t s,
+                            int kv_heads = 0);  // (kv_heads: a GQA handle's, else 0 / heads)
 hipError_t launch_commit(const char *blob, int C, const uint16_t *stage,
                          uint16_t *kc, uint16_t *vc, int heads, int d, int slots,
                          hipStream_t s);
@@ -301,7 +302,8 @@ hipError_t launch_attention(const char *blob, int W, int max_q, uint16_t *qbuf, 
                             hipStream_t s, bool out_packed, bool fused, int T, int C,
                             const uint16_t *qkv, Partials qkvp, uint16_t *stage_wr,
                             const uint16_t *stage_rd, const float *rope, int max_rope_pos,
-                            const OprojArgs *opa = nullptr);
+                            const OprojArgs *opa = nullptr, int kv_heads = 0,
+                            bool gqa_shared = false);  // (a GQA handle: its K/V heads, its form)
 
 uint64_t weight_key(const char *name, uint64_t seed);
 

@@ -32,6 +32,11 @@
 // softmax state and merge through LDS.  Every key/value byte of a request is
 // read once per 16-query tile (the reference's tree kernel re-reads the
 // whole K/V once per query, tree_inc...cu:135).
+//
+// Grouped-query attention (a handle of ffmi_attn_create_gqa; an extension,
+// the reference replicates K/V per query head on load): `head` of both caches
+// and of the TREE staging rows runs over the handle's K/V heads, and query
+// head h uses K/V head h / (heads / kv_heads); see attention_kernel's GM.
 #include <stdlib.h>
 
 #include <algorithm>
@@ -102,9 +107,16 @@ __device__ __forceinline__ void st_h4(uint16_t *p, uint16_t a, uint16_t b, uint1
 // PSRC: 1 = qkv from split-K slabs, 0 = fp16 qkv, -1 = decided at run time
 // by `part` (a compile-time source keeps the two load paths from joining:
 // the join's register copies waited for half of the slab loads).
-template <int D, int NQ, int NT, int PSRC = -1, class AfterLoads, class BeforeStores>
+// GQA (attention_kernel, GM): query head h reads and writes K/V head hk of
+// kvh (MHA: hk = h, kvh = heads); the qkv row is [heads D | kvh D | kvh D] and
+// a staging row holds 2 kvh D values.  GS (the group-shared form): the NQ
+// units' rows are tile rows r = q * gq + m -- token q of the item, query head
+// hk * gq + m -- and only a token's m == 0 row stores its K/V.
+template <int D, int NQ, int NT, int PSRC = -1, bool GS = false, class AfterLoads,
+          class BeforeStores>
 __device__ __forceinline__ void kv_update_item(
-    const BatchView &bv, const WorkDev *__restrict__ wdp, int h, int heads, int slots, int T,
+    const BatchView &bv, const WorkDev *__restrict__ wdp, int h, int heads, int hk, int kvh,
+    int gq, int slots, int T,
     const uint16_t *__restrict__ qkv, const float *__restrict__ part, int pS, int pNP,
     const float *__restrict__ rope, int max_rope_pos, uint16_t *__restrict__ qbuf,
     uint16_t *__restrict__ kc, uint16_t *__restrict__ stage_wr, uint16_t (*sV)[NQ + 1],
@@ -112,12 +124,13 @@ __device__ __forceinline__ void kv_update_item(
     uint16_t (*sVt)[kTailSlots + 8], int tail0, AfterLoads &&after_loads,
     BeforeStores &&before_stores) {
   constexpr int HD = D / 2, G = HD / 4, UNITS = NQ * G, U = (UNITS + NT - 1) / NT;
-  const int Hl = heads * D;
+  const int Hl = heads * D, Hkv = kvh * D, RW = Hl + 2 * Hkv;
   const ffmi_attn_work w = wdp->w;
   // channels: 0 q lo, 1 q hi, 2 k lo, 3 k hi, 4 v lo, 5 v hi
   f4 x[U][6], y[U][6], cs[U][2];  // y: second fp32 slab
   int tslot[U], treq[U];  // (scalar fields: a struct copy would go to scratch)
   int tl[U], i0[U];
+  int tq[U], hq[U];  // token of the item and query head of unit u (GS: from its tile row)
   // One round trip for every prologue load.  The RoPE positions of the
   // item's tokens come through the scalar cache (16 dwords of the work item,
   // lgkmcnt; readfirstlane keeps them there -- the per-lane select over them
@@ -135,13 +148,15 @@ __device__ __forceinline__ void kv_update_item(
   for (int u = 0; u < U; ++u) {
     const int e = min((int)threadIdx.x + u * NT, UNITS - 1);
     tl[u] = e / G, i0[u] = (e % G) * 4;
+    tq[u] = GS ? tl[u] / gq : tl[u];
+    hq[u] = GS ? hk * gq + tl[u] % gq : h;
   }
 #pragma unroll
   for (int u = 0; u < U; ++u) {
-    const int t = w.q_start + (tl[u] < w.q_count ? tl[u] : 0);
-    const int col[6] = {h * D + i0[u], h * D + i0[u] + HD, Hl + h * D + i0[u],
-                        Hl + h * D + i0[u] + HD, 2 * Hl + h * D + i0[u],
-                        2 * Hl + h * D + i0[u] + HD};
+    const int t = w.q_start + (tq[u] < w.q_count ? tq[u] : 0);
+    const int col[6] = {hq[u] * D + i0[u], hq[u] * D + i0[u] + HD, Hl + hk * D + i0[u],
+                        Hl + hk * D + i0[u] + HD, Hl + Hkv + hk * D + i0[u],
+                        Hl + Hkv + hk * D + i0[u] + HD};
     if (PSRC == 1 || (PSRC < 0 && part)) {  // slabs 0 and 1 (slab 0 again when pS == 1: no branch)
       const float *p1 = part + (pS > 1 ? (size_t)T * pNP : 0);
 #pragma unroll
@@ -153,14 +168,14 @@ __device__ __forceinline__ void kv_update_item(
     } else {  // raw fp16 bits now, converted after every load is out
 #pragma unroll
       for (int c = 0; c < 6; ++c) {
-        const uint2 r = *reinterpret_cast<const uint2 *>(qkv + (size_t)t * 3 * Hl + col[c]);
+        const uint2 r = *reinterpret_cast<const uint2 *>(qkv + (size_t)t * RW + col[c]);
         y[u][c] = f4{__uint_as_float(r.x), __uint_as_float(r.y), 0.f, 0.f};
       }
     }
   }
 #pragma unroll
   for (int u = 0; u < U; ++u) {
-    const int q = tl[u] < w.q_count ? tl[u] : 0;
+    const int q = tq[u] < w.q_count ? tq[u] : 0;
     uint32_t wd = rpw[0];
 #pragma unroll
     for (int j = 1; j < FFMI_ATTN_QTILE / 2; ++j) wd = (q >> 1) == j ? rpw[j] : wd;
@@ -171,7 +186,7 @@ __device__ __forceinline__ void kv_update_item(
   }
 #pragma unroll
   for (int u = 0; u < U; ++u) {
-    const int t = w.q_start + (tl[u] < w.q_count ? tl[u] : 0);
+    const int t = w.q_start + (tq[u] < w.q_count ? tq[u] : 0);
     tslot[u] = bv.tokens[t].store_slot;
     treq[u] = bv.tokens[t].req;
   }
@@ -199,10 +214,10 @@ __device__ __forceinline__ void kv_update_item(
     for (int sl = 2; sl < pS; ++sl)
 #pragma unroll
       for (int u = 0; u < U; ++u) {
-        const int t = w.q_start + (tl[u] < w.q_count ? tl[u] : 0);
-        const int col[6] = {h * D + i0[u], h * D + i0[u] + HD, Hl + h * D + i0[u],
-                            Hl + h * D + i0[u] + HD, 2 * Hl + h * D + i0[u],
-                            2 * Hl + h * D + i0[u] + HD};
+        const int t = w.q_start + (tq[u] < w.q_count ? tq[u] : 0);
+        const int col[6] = {hq[u] * D + i0[u], hq[u] * D + i0[u] + HD, Hl + hk * D + i0[u],
+                            Hl + hk * D + i0[u] + HD, Hl + Hkv + hk * D + i0[u],
+                            Hl + Hkv + hk * D + i0[u] + HD};
 #pragma unroll
         for (int c = 0; c < 6; ++c)
           x[u][c] += *reinterpret_cast<const f4 *>(part + sl * slab + (size_t)t * pNP + col[c]);
@@ -217,8 +232,8 @@ __device__ __forceinline__ void kv_update_item(
   // ---- stores
 #pragma unroll
   for (int u = 0; u < U; ++u) {
-    if (tl[u] >= w.q_count || (int)threadIdx.x + u * NT >= UNITS) continue;
-    const int t = w.q_start + tl[u];
+    if (tq[u] >= w.q_count || (int)threadIdx.x + u * NT >= UNITS) continue;
+    const int t = w.q_start + tq[u];
     uint16_t qlo[4], qhi[4], klo[4], khi[4], vlo[4], vhi[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -232,16 +247,17 @@ __device__ __forceinline__ void kv_update_item(
       vhi[j] = f2h(x[u][5][j]);
     }
     // rotated q: to LDS for the same workgroup's attention (fused), else HBM
-    uint16_t *qo = sQ ? &sQ[tl[u]][i0[u]] : qbuf + (size_t)t * Hl + h * D + i0[u];
+    uint16_t *qo = sQ ? &sQ[tl[u]][i0[u]] : qbuf + (size_t)t * Hl + hq[u] * D + i0[u];
     st_h4(qo, qlo[0], qlo[1], qlo[2], qlo[3]);
     st_h4(qo + HD, qhi[0], qhi[1], qhi[2], qhi[3]);
+    if (GS && tl[u] % gq != 0) continue;  // the token's K/V: its first row only
     const bool store = tslot[u] >= 0 && tslot[u] < slots;
     if (store) {
-      uint16_t *kr = kc + (((size_t)treq[u] * heads + h) * slots + tslot[u]) * D + i0[u];
+      uint16_t *kr = kc + (((size_t)treq[u] * kvh + hk) * slots + tslot[u]) * D + i0[u];
       st_h4(kr, klo[0], klo[1], klo[2], klo[3]);
       st_h4(kr + HD, khi[0], khi[1], khi[2], khi[3]);
     }
-    if (i0[u] == 0) sSlot[tl[u]] = store ? tslot[u] : -1;
+    if (i0[u] == 0) sSlot[tq[u]] = store ? tslot[u] : -1;
     if (sKt) {  // (host-checked: every stored slot lies in the tail)
       if (store) {
         const int ts = tslot[u] - tail0;
@@ -256,16 +272,16 @@ __device__ __forceinline__ void kv_update_item(
     } else {
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        sV[i0[u] + j][tl[u]] = vlo[j];
-        sV[i0[u] + HD + j][tl[u]] = vhi[j];
+        sV[i0[u] + j][tq[u]] = vlo[j];
+        sV[i0[u] + HD + j][tq[u]] = vhi[j];
       }
     }
     if (stage_wr) {
-      uint16_t *st = stage_wr + (size_t)t * 2 * Hl + h * D + i0[u];
+      uint16_t *st = stage_wr + (size_t)t * 2 * Hkv + hk * D + i0[u];
       st_h4(st, klo[0], klo[1], klo[2], klo[3]);
       st_h4(st + HD, khi[0], khi[1], khi[2], khi[3]);
-      st_h4(st + Hl, vlo[0], vlo[1], vlo[2], vlo[3]);
-      st_h4(st + Hl + HD, vhi[0], vhi[1], vhi[2], vhi[3]);
+      st_h4(st + Hkv, vlo[0], vlo[1], vlo[2], vlo[3]);
+      st_h4(st + Hkv + HD, vhi[0], vhi[1], vhi[2], vhi[3]);
     }
   }
 }
@@ -292,60 +308,77 @@ __device__ __forceinline__ void kv_store_vt(const ffmi_attn_work &w, int h, int 
 // than the one this step writes (stage_wr), so both run in one launch; the
 // host launches commits separately first when a commit depth coincides with
 // a slot this step stores (the reference's commit-then-store order).
-template <int D>
+// GQ (a GQA handle, kvh_ < heads K/V heads): still one workgroup per (item,
+// query head h); it rotates its own q and the K/V of head h / (heads / kvh_),
+// so the members of a group store the same values to the same addresses.
+template <int D, bool GQ = false>
 __global__ __launch_bounds__(FFMI_ATTN_QTILE * D / 8) void kv_update_kernel(
     const char *__restrict__ blob, int T, int W, int C, const uint16_t *__restrict__ qkv,
     const float *__restrict__ part, int pS, int pNP, uint16_t *__restrict__ qbuf,
     uint16_t *__restrict__ kc, uint16_t *__restrict__ vc, uint16_t *__restrict__ stage_wr,
     const uint16_t *__restrict__ stage_rd, const float *__restrict__ rope, int heads, int slots,
-    int max_rope_pos) {
+    int max_rope_pos, int kvh_) {
   constexpr int NQ = FFMI_ATTN_QTILE;
   constexpr int NT = NQ * D / 8;
   __shared__ uint16_t sV[D][NQ + 1];
   __shared__ int sSlot[NQ];
-  const int Hl = heads * D;
   const BatchView bv = batch_view(blob);
   const int item = blockIdx.x / heads, h = blockIdx.x % heads;
+  const int kvh = GQ ? kvh_ : heads, gq = GQ ? heads / kvh_ : 1, hk = GQ ? h / gq : h;
+  const int Hkv = kvh * D;
   if (item >= W) {  // ---- commit block (tree_inc...cu:335-396)
     const int ci = item - W;
     if (ci >= C) return;
     const ffmi_commit_info cm = bv.commits[ci];
     if (cm.depth < 0 || cm.depth >= slots) return;
-    const uint16_t *st = stage_rd + (size_t)cm.src_token * 2 * Hl + h * D;
+    const uint16_t *st = stage_rd + (size_t)cm.src_token * 2 * Hkv + hk * D;
     const int i = threadIdx.x;
     if (i < D) {
-      kc[(((size_t)cm.req * heads + h) * slots + cm.depth) * D + i] = st[i];
-      vc[(((size_t)cm.req * heads + h) * D + i) * slots + cm.depth] = st[Hl + i];
+      kc[(((size_t)cm.req * kvh + hk) * slots + cm.depth) * D + i] = st[i];
+      vc[(((size_t)cm.req * kvh + hk) * D + i) * slots + cm.depth] = st[Hkv + i];
     }
     return;
   }
   const ffmi_attn_work w = bv.work[item].w;
-  kv_update_item<D, NQ, NT>(bv, &bv.work[item], h, heads, slots, T, qkv, part, pS, pNP, rope,
-                            max_rope_pos, qbuf, kc, stage_wr, sV, sSlot, nullptr, nullptr, nullptr,
-                            0, [] {}, [] {});
+  kv_update_item<D, NQ, NT>(bv, &bv.work[item], h, heads, hk, kvh, gq, slots, T, qkv, part, pS,
+                            pNP, rope, max_rope_pos, qbuf, kc, stage_wr, sV, sSlot, nullptr,
+                            nullptr, nullptr, 0, [] {}, [] {});
   __syncthreads();
-  kv_store_vt<D, NQ>(w, h, heads, slots, vc, sV, sSlot);
+  kv_store_vt<D, NQ>(w, hk, kvh, slots, vc, sV, sSlot);
 }
 
 hipError_t launch_kv_update(const char *blob, int T, int W, int C, const uint16_t *qkv,
                             Partials qkvp, uint16_t *qbuf, uint16_t *kc, uint16_t *vc,
                             uint16_t *stage_wr, const uint16_t *stage_rd, const float *rope,
-                            int heads, int d, int slots, int max_rope_pos, hipStream_t s) {
+                            int heads, int d, int slots, int max_rope_pos, hipStream_t s,
+                            int kv_heads) {
   if (W <= 0 && C <= 0) return hipSuccess;
   const dim3 grid((W + C) * heads);
   const float *pp = qkvp.S > 0 ? qkvp.p : nullptr;
+  if (kv_heads > 0 && kv_heads != heads) {  // a GQA handle (fp16 qkv, d 64 / 128: api.cpp)
+    if (heads % kv_heads || pp || (d != 128 && d != 64)) return hipErrorInvalidValue;
+    if (d == 128)
+      hipLaunchKernelGGL((kv_update_kernel<128, true>), grid, dim3(FFMI_ATTN_QTILE * 16), 0, s,
+                         blob, T, W, C, qkv, pp, 0, 0, qbuf, kc, vc, stage_wr, stage_rd, rope,
+                         heads, slots, max_rope_pos, kv_heads);
+    else
+      hipLaunchKernelGGL((kv_update_kernel<64, true>), grid, dim3(FFMI_ATTN_QTILE * 8), 0, s, blob,
+                         T, W, C, qkv, pp, 0, 0, qbuf, kc, vc, stage_wr, stage_rd, rope, heads,
+                         slots, max_rope_pos, kv_heads);
+    return hipGetLastError();
+  }
   if (d == 128)
     hipLaunchKernelGGL(kv_update_kernel<128>, grid, dim3(FFMI_ATTN_QTILE * 16), 0, s, blob, T, W, C, qkv, pp,
                        qkvp.S, qkvp.NP, qbuf, kc, vc, stage_wr, stage_rd, rope, heads, slots,
-                       max_rope_pos);
+                       max_rope_pos, heads);
   else if (d == 64)
     hipLaunchKernelGGL(kv_update_kernel<64>, grid, dim3(FFMI_ATTN_QTILE * 8), 0, s, blob, T, W, C, qkv, pp,
                        qkvp.S, qkvp.NP, qbuf, kc, vc, stage_wr, stage_rd, rope, heads, slots,
-                       max_rope_pos);
+                       max_rope_pos, heads);
   else if (d == 32)  // (incremental decoding only: ffmi_attn_create)
     hipLaunchKernelGGL(kv_update_kernel<32>, grid, dim3(FFMI_ATTN_QTILE * 4), 0, s, blob, T, W, C, qkv, pp,
                        qkvp.S, qkvp.NP, qbuf, kc, vc, stage_wr, stage_rd, rope, heads, slots,
-                       max_rope_pos);
+                       max_rope_pos, heads);
   else
     return hipErrorInvalidValue;
   return hipGetLastError();
@@ -370,6 +403,7 @@ struct KvUpdateArgs {
   const float *rope;
   int max_rope_pos;
   long long *stamps;  // ST kernels: per-wave timeline (diagnostics)
+  int kvh;            // GM != 0: K/V heads of the handle
 };
 
 // One workgroup per (work item = <= 16*QT consecutive queries of a request,
@@ -398,14 +432,30 @@ struct KvUpdateArgs {
 // its own 16: the key loop and merge work per workgroup halve.  Per query the
 // arithmetic is the QT == 2 kernel's (MFMA columns are independent), so the
 // output is bit-identical.
+//
+// GM (a GQA handle: kv.kvh K/V heads, gq = heads / kv.kvh query heads each;
+// caches [req][kv head][..], staging rows of 2 kvh D):
+//  1 kv-indexed: the grid and every route above as for MHA, but query head h
+//    reads -- and, in the fused prologue, writes -- K/V head h / gq.  The gq
+//    workgroups of a group store the same values to the same addresses, and
+//    read from memory only slots below the tail, as the QS == 2 pair does.
+//  2 group-shared (QT == 1, QS == 1, no OP; items of <= 16 / gq queries):
+//    blockIdx.y is the K/V head; tile row r = q * gq + m carries query q of
+//    head hk * gq + m, the gq rows of a query share its visibility record, and
+//    every K / V^T fragment is loaded once for the group.  Chunk striding,
+//    softmax state and merge are per tile row exactly as above, so each
+//    head's output is bit-identical to GM == 1's (and to an MHA handle's over
+//    replicated K/V).
 template <int D, int QT, int NW, bool FUSED, bool ST = false, int PSRC = -1, bool OP = false,
-          int QS = 1>
+          int QS = 1, int GM = 0>
 __global__ __launch_bounds__(64 * NW, 1) void attention_kernel(
     const char *__restrict__ blob, uint16_t *__restrict__ qbuf, uint16_t *__restrict__ kc,
     uint16_t *__restrict__ vc, uint16_t *__restrict__ out, int heads, int slots, float scale,
     int out_packed, KvUpdateArgs kv, OprojArgs opa) {
   static_assert(!OP || (FUSED && QT == 1 && QS == 1), "output projection: fused, one query tile");
   static_assert(QS == 1 || (FUSED && QT == 1 && QS == 2), "query split: fused, 2 x 16 queries");
+  static_assert(GM == 0 || (!OP && PSRC <= 0), "GQA: fp16 qkv, no output projection");
+  static_assert(GM != 2 || (QT == 1 && QS == 1), "group-shared: one query tile");
   constexpr int KS = D / 32;  // k-steps of the QK^T product
   constexpr int DT = D / 16;  // d-tiles of the PV product
   constexpr int NQ = 16 * QT;   // queries this workgroup attends
@@ -436,14 +486,16 @@ __global__ __launch_bounds__(64 * NW, 1) void attention_kernel(
   const int wave = threadIdx.x >> 6;
   const int qi = lane & 15;
   const int g = lane >> 4;
-  const int h = blockIdx.y;
+  const int kvh = GM ? kv.kvh : heads, gq = GM ? heads / kv.kvh : 1;
+  const int hk = GM == 1 ? (int)blockIdx.y / gq : (int)blockIdx.y;  // K/V head
+  const int h = GM == 2 ? hk * gq : (int)blockIdx.y;  // query head (GM == 2: the group's first)
   const BatchView bv = batch_view(blob);
   // (fields, not a copy of the WorkDev: a private copy of its rope_pos array
   // would be indexed per lane and live in scratch)
   const ffmi_attn_work w = bv.work[blockIdx.x].w;
-  const int Hl = heads * D;
-  const uint16_t *kbase = kc + ((size_t)w.req * heads + h) * slots * D;
-  const uint16_t *vbase = vc + ((size_t)w.req * heads + h) * D * slots;
+  const int Hl = heads * D, Hkv = kvh * D;
+  const uint16_t *kbase = kc + ((size_t)w.req * kvh + hk) * slots * D;
+  const uint16_t *vbase = vc + ((size_t)w.req * kvh + hk) * D * slots;
   // K rows and V^T columns of one 32-key chunk (chunk indices are clamped by
   // the caller: the cache is allocated to a multiple of 32 slots)
   auto load_chunk = [&](int c, h8 (&kf)[2][KS], h8 (&va)[DT]) {
@@ -538,8 +590,9 @@ __global__ __launch_bounds__(64 * NW, 1) void attention_kernel(
       csrc[i] = (int)(int16_t)((j & 1) ? (wd >> 16) : (wd & 0xffffu));
     }
     uint4 cmv[CP];
-    kv_update_item<D, NQK, NT, PSRC>(
-        bv, wdp, h, heads, slots, kv.T, kv.qkv, kv.part, kv.pS, kv.pNP, kv.rope, kv.max_rope_pos,
+    kv_update_item<D, NQK, NT, PSRC, GM == 2>(
+        bv, wdp, h, heads, hk, kvh, gq, slots, kv.T, kv.qkv, kv.part, kv.pS, kv.pNP, kv.rope,
+        kv.max_rope_pos,
         qbuf, kc, kv.stage_wr, nullptr, sSlot, sQ, sKt, sVt, tail0,
         [&] {  // after the KV update's own loads: commits, tail, first chunk
 #pragma unroll
@@ -548,7 +601,8 @@ __global__ __launch_bounds__(64 * NW, 1) void attention_kernel(
             if (j < ncm) {
               const int src = csrc[i];
               cmv[i] = *reinterpret_cast<const uint4 *>(
-                  kv.stage_rd + (size_t)src * 2 * Hl + (r >= D8 ? Hl : 0) + h * D + (r % D8) * 8);
+                  kv.stage_rd + (size_t)src * 2 * Hkv + (r >= D8 ? Hkv : 0) + hk * D +
+                  (r % D8) * 8);
             }
           }
 #pragma unroll
@@ -611,11 +665,11 @@ __global__ __launch_bounds__(64 * NW, 1) void attention_kernel(
             if (dep < 0 || dep >= slots) continue;
             const int ts = dep - tail0;
             if (r < D8) {
-              *reinterpret_cast<uint4 *>(kc + (((size_t)w.req * heads + h) * slots + dep) * D + i8) =
+              *reinterpret_cast<uint4 *>(kc + (((size_t)w.req * kvh + hk) * slots + dep) * D + i8) =
                   cmv[i];
               *reinterpret_cast<uint4 *>(&sKt[ts][i8]) = cmv[i];
             } else {
-              uint16_t *vt = vc + (((size_t)w.req * heads + h) * D + i8) * slots + dep;
+              uint16_t *vt = vc + (((size_t)w.req * kvh + hk) * D + i8) * slots + dep;
               const uint32_t vw[4] = {cmv[i].x, cmv[i].y, cmv[i].z, cmv[i].w};
 #pragma unroll
               for (int jj = 0; jj < 8; ++jj) {
@@ -640,7 +694,9 @@ __global__ __launch_bounds__(64 * NW, 1) void attention_kernel(
   h8 qf[QT][KS];
 #pragma unroll
   for (int qt = 0; qt < QT; ++qt) {
-    const int q = qbase + qt * 16 + qi;
+    const int row = qbase + qt * 16 + qi;          // of the item's tile
+    const int q = GM == 2 ? row / gq : row;         // token of the item
+    const int hq = GM == 2 ? h + row % gq : h;      // its query head
     qvalid[qt] = q < w.q_count;
     if (FUSED) {
       const int4 mr = sMrec[qvalid[qt] ? q : 0];
@@ -652,9 +708,9 @@ __global__ __launch_bounds__(64 * NW, 1) void attention_kernel(
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks)
       qf[qt][ks] = !qvalid[qt] ? h8{0, 0, 0, 0, 0, 0, 0, 0}
-                   : FUSED ? *reinterpret_cast<const h8 *>(&sQ[q][32 * ks + 8 * g])
+                   : FUSED ? *reinterpret_cast<const h8 *>(&sQ[row][32 * ks + 8 * g])
                            : *reinterpret_cast<const h8 *>(
-                                 qbuf + (size_t)(w.q_start + q) * Hl + h * D + 32 * ks + 8 * g);
+                                 qbuf + (size_t)(w.q_start + q) * Hl + hq * D + 32 * ks + 8 * g);
   }
 
   const float NEG = -INFINITY;
@@ -749,7 +805,7 @@ __global__ __launch_bounds__(64 * NW, 1) void attention_kernel(
   if (FUSED) {
     // V^T of this step's tokens to HBM from the tail, by each wave once its
     // key loop is done (not waited for)
-    uint16_t *vt = vc + ((size_t)w.req * heads + h) * D * slots;
+    uint16_t *vt = vc + ((size_t)w.req * kvh + hk) * D * slots;
     for (int e = threadIdx.x; e < D * NQK; e += blockDim.x) {
       const int dd = e / NQK, tt = e % NQK;
       if (tt >= w.q_count) continue;
@@ -779,7 +835,8 @@ __global__ __launch_bounds__(64 * NW, 1) void attention_kernel(
   // merge: wave w finalizes d-tiles t = w, w+NW, ... of every query tile
 #pragma unroll
   for (int qt = 0; qt < QT; ++qt) {
-    const int ql = qt * 16 + qi, q = qbase + ql;  // in the workgroup / in the item
+    const int ql = qt * 16 + qi, row = qbase + ql;  // in the workgroup / in the item's tile
+    const int q = GM == 2 ? row / gq : row, hq = GM == 2 ? h + row % gq : h;
     float M = NEG;
 #pragma unroll
     for (int ww = 0; ww < NW; ++ww) M = fmaxf(M, sm_m[ww][ql]);
@@ -793,7 +850,7 @@ __global__ __launch_bounds__(64 * NW, 1) void attention_kernel(
     const float inv = 1.0f / (L + 1e-6f);
     if (!qvalid[qt]) continue;
     const int orow_m = w.q_start + q;
-    uint16_t *orow = out + (size_t)orow_m * Hl + h * D;
+    uint16_t *orow = out + (size_t)orow_m * Hl + hq * D;
     for (int t = wave; t < DT; t += NW) {
       uint16_t r4[4];
 #pragma unroll
@@ -806,11 +863,11 @@ __global__ __launch_bounds__(64 * NW, 1) void attention_kernel(
       uint2 pk;
       pk.x = r4[0] | ((uint32_t)r4[1] << 16);
       pk.y = r4[2] | ((uint32_t)r4[3] << 16);
-      uint16_t *dst = out_packed ? out + act_packed_off(orow_m, h * D + t * 16 + 4 * g, Hl)
+      uint16_t *dst = out_packed ? out + act_packed_off(orow_m, hq * D + t * 16 + 4 * g, Hl)
                                  : orow + t * 16 + 4 * g;
       *reinterpret_cast<uint2 *>(dst) = pk;
       // OP: the rounded row also to LDS (the queries' tile is free by now)
-      if (OP) *reinterpret_cast<uint2 *>(&sQ[q][t * 16 + 4 * g]) = pk;
+      if (OP) *reinterpret_cast<uint2 *>(&sQ[row][t * 16 + 4 * g]) = pk;
     }
   }
   if constexpr (OP) {
@@ -938,6 +995,39 @@ static hipError_t launch_attention_d(const char *blob, int W, int max_q, uint16_
   return hipGetLastError();
 }
 
+// A GQA handle's launch (kv.kvh < heads; fp16 qkv, no output projection, no
+// stamps).  shared: the group-shared form, one workgroup per (item, K/V
+// head) -- the caller checked max_q * (heads / kv.kvh) <= 16; otherwise the
+// kv-indexed forms on the MHA grid, query split included.
+template <int D>
+static hipError_t launch_attention_gqa(const char *blob, int W, int max_q, uint16_t *qbuf,
+                                       uint16_t *kc, uint16_t *vc, uint16_t *out, int heads,
+                                       int slots, float scale, hipStream_t s, int op, bool fused,
+                                       bool shared, const KvUpdateArgs &kv) {
+  const dim3 grid(W, heads);
+#define FFMI_ATT_G(QT, FU, QS, GM, GRID)                                                       \
+  hipLaunchKernelGGL((attention_kernel<D, QT, 8, FU, false, (FU ? 0 : -1), false, QS, GM>), GRID, \
+                     dim3(512), 0, s, blob, qbuf, kc, vc, out, heads, slots, scale, op, kv,      \
+                     OprojArgs())
+  if (shared) {
+    if (max_q * (heads / kv.kvh) > 16) return hipErrorInvalidValue;
+    const dim3 gridk(W, kv.kvh);
+    if (fused) FFMI_ATT_G(1, true, 1, 2, gridk);
+    else FFMI_ATT_G(1, false, 1, 2, gridk);
+  } else if (max_q > 16 && fused && attn_qsplit(W * heads)) {
+    const dim3 grid2(W, heads, 2);
+    FFMI_ATT_G(1, true, 2, 1, grid2);
+  } else if (max_q <= 16) {
+    if (fused) FFMI_ATT_G(1, true, 1, 1, grid);
+    else FFMI_ATT_G(1, false, 1, 1, grid);
+  } else {
+    if (fused) FFMI_ATT_G(2, true, 1, 1, grid);
+    else FFMI_ATT_G(2, false, 1, 1, grid);
+  }
+#undef FFMI_ATT_G
+  return hipGetLastError();
+}
+
 // FFMI_ATTN_STAMP=1: d = 128 launches record a per-wave timeline
 // {start, after prologue, before k-loop, after k-loop, after merge barrier,
 // end, [fused] after commits, after KV update, after its barrier, after the
@@ -998,14 +1088,26 @@ hipError_t launch_attention(const char *blob, int W, int max_q, uint16_t *qbuf, 
                             hipStream_t s, bool out_packed, bool fused, int T, int C,
                             const uint16_t *qkv, Partials qkvp, uint16_t *stage_wr,
                             const uint16_t *stage_rd, const float *rope, int max_rope_pos,
-                            const OprojArgs *opa) {
+                            const OprojArgs *opa, int kv_heads, bool gqa_shared) {
   if (W <= 0) return hipSuccess;
   if (out_packed && (heads * d) % 32) return hipErrorInvalidValue;
   if (max_q > FFMI_ATTN_QTILE) return hipErrorInvalidValue;
+  const bool gqa = kv_heads > 0 && kv_heads != heads;
   const KvUpdateArgs kv{T,        C,        qkv,  qkvp.S > 0 ? qkvp.p : nullptr,
                         qkvp.S,   qkvp.NP,  stage_wr, stage_rd,
-                        rope,     max_rope_pos, attn_stamp_buf(W * heads)};
+                        rope,     max_rope_pos, gqa ? nullptr : attn_stamp_buf(W * heads),
+                        gqa ? kv_heads : heads};
   const int op = out_packed ? 1 : 0;
+  if (gqa) {  // (api.cpp: fp16 qkv, d 64 / 128, no output projection)
+    if (heads % kv_heads || kv.part || opa) return hipErrorInvalidValue;
+    if (d == 128)
+      return launch_attention_gqa<128>(blob, W, max_q, qbuf, kc, vc, out, heads, slots, scale, s,
+                                       op, fused, gqa_shared, kv);
+    if (d == 64)
+      return launch_attention_gqa<64>(blob, W, max_q, qbuf, kc, vc, out, heads, slots, scale, s,
+                                      op, fused, gqa_shared, kv);
+    return hipErrorInvalidValue;
+  }
   if (opa) {  // output projection folded in (the caller checked fused, d, max_q, N)
     if (!fused || d != 64 || max_q > 16 || opa->N % 16 || opa->N > 16 * 8 * 8 || T > opa->max_T)
       return hipErrorInvalidValue;

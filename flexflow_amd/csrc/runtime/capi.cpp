@@ -17,6 +17,20 @@ extern "C" ffmi_status ffmi_model_create(const ffmi_llama_config *cfg, const ffm
   return ffmi::create_llama_gpu(cfg, o, out);
 }
 
+extern "C" ffmi_status ffmi_model_create_ex(const ffmi_llama_config *cfg, const ffmi_model_opts *o,
+                                            unsigned flags, ffmi_model **out) {
+  if (!flags) return ffmi_model_create(cfg, o, out);
+  FFMI_CHECK(cfg && o && out && (flags & ~FFMI_MODEL_NATIVE_GQA) == 0, FFMI_ERR_INVALID);
+  if (o->full_precision) {  // the fp32 model replicates K/V, as the reference does
+    ffmi_set_last_error("native_gqa: fp16 models only (full_precision replicates K/V)", __FILE__,
+                        __LINE__);
+    return FFMI_ERR_UNSUPPORTED;
+  }
+  return ffmi::create_llama_gpu(cfg, o, out, flags);
+}
+
+extern "C" size_t ffmi_model_kv_cache_bytes(ffmi_model *m) { return m ? m->kv_cache_bytes() : 0; }
+
 extern "C" void ffmi_model_destroy(ffmi_model *m) { delete m; }
 
 extern "C" ffmi_status ffmi_model_set_profiling(ffmi_model *m, int level) {

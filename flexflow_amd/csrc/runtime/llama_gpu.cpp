@@ -43,6 +43,11 @@ struct LlamaGPU : public ffmi_model {
   bool uses_collectives() const override { return o.tp_size > 1; }
   std::string weights_folder;  // reference-format checkpoint ("" = synthetic)
   int Hl = 0, Fl = 0, d = 0, heads_l = 0, slots = 0;
+  // FFMI_MODEL_NATIVE_GQA with num_kv_heads < num_heads: this rank's K/V heads,
+  // their width and the qkv row [Hl | Hkv | Hkv]; otherwise K/V are (or are
+  // replicated to) heads_l heads: kvh_l = heads_l, Hkv = Hl, Nqkv = 3 Hl
+  bool native_gqa = false;
+  int kvh_l = 0, Hkv = 0, Nqkv = 0;
   // GEMM inputs (normed hidden, attention output, SiLU output) are kept in
   // packed activation tiles: every GEMM then reads its activation fragments
   // as contiguous 1 KiB blocks, like the weights (see act_packed_off)
@@ -293,8 +298,8 @@ struct LlamaGPU : public ffmi_model {
     std::vector<int> kv(o.max_requests, 0);
     for (const auto &w : ps.work) kv[w.req] = std::max(kv[w.req], w.kv_len);
     double b = 0;
-    for (int r : kv) b += (double)r * Hl * 2 * 2;
-    return b + (double)ps.tokens.size() * (3 * Hl + Hl) * 2;
+    for (int r : kv) b += (double)r * Hkv * 2 * 2;
+    return b + (double)ps.tokens.size() * (Nqkv + Hl) * 2;
   }
 
   // ---- tensor capture (--inference-debugging, operator.h:271-360) ----
@@ -306,10 +311,15 @@ struct LlamaGPU : public ffmi_model {
   uint16_t *dbg_buf = nullptr;
   size_t dbg_off[kDbgKinds] = {};
   int dbg_T = -1;
+  size_t kv_cache_bytes() const override {
+    size_t b = 0;
+    for (const auto &L : layers) b += ffmi_attn_cache_bytes(L.attn);
+    return b;
+  }
   long debug_width(int k) const override {
     switch (k) {
       case FFMI_DBG_LOGITS: return Vl;
-      case FFMI_DBG_QKV: return 3L * Hl;
+      case FFMI_DBG_QKV: return Nqkv;
       case FFMI_DBG_ATTN_OUT: return Hl;
       case FFMI_DBG_MLP_ACT: return Fl;
       case FFMI_DBG_HIDDEN: case FFMI_DBG_ATTN_NORM: case FFMI_DBG_O_PROJ:
@@ -401,7 +411,7 @@ struct LlamaGPU : public ffmi_model {
       st = FFMI_ERR_HIP;
     }
     if (st == FFMI_OK) {
-      const int pitch = 3 * (Hl / 16);
+      const int pitch = Nqkv / 16;
       const hipError_t e0 = launch_pack_weight(tmp, H, s * Hl + (swap ? d : 0), 0, d, H,
                                                layers[l].wqkv, 1, 0, pitch, stream);
       const hipError_t e1 = launch_pack_weight(tmp, H, s * Hl + (swap ? 0 : d), 0, d, H,
@@ -520,7 +530,7 @@ struct LlamaGPU : public ffmi_model {
     std::string file = hf_name.rfind("model.", 0) == 0 ? hf_name.substr(6) : hf_name;
     const bool kv = file.find("self_attn.k_proj") != std::string::npos ||
                     file.find("self_attn.v_proj") != std::string::npos;
-    const int group = kv ? c.num_heads / c.num_kv_heads : 1;
+    const int group = kv && !native_gqa ? c.num_heads / c.num_kv_heads : 1;  // (native: as stored)
     const size_t n_file = n / group;
     const std::string path = weights_folder + "/" + file;
     FILE *f = fopen(path.c_str(), "rb");
@@ -563,24 +573,39 @@ struct LlamaGPU : public ffmi_model {
   ffmi_status init() {
     const int H = c.hidden, F = c.intermediate, V = c.vocab_size, P = o.tp_size;
     // GQA checkpoints load with K/V replicated per query head (the
-    // reference's layout); synthetic weights are MHA only
+    // reference's layout) and synthetic weights are MHA only -- unless the
+    // model was created with FFMI_MODEL_NATIVE_GQA: K/V at num_kv_heads, from
+    // a checkpoint or the generator, each rank its own K/V heads
+    native_gqa = native_gqa && c.num_kv_heads != c.num_heads;
     FFMI_CHECK(c.num_kv_heads == c.num_heads ||
-                   (!weights_folder.empty() && c.num_kv_heads > 0 &&
+                   ((native_gqa || !weights_folder.empty()) && c.num_kv_heads > 0 &&
                     c.num_heads % c.num_kv_heads == 0),
                FFMI_ERR_UNSUPPORTED);
     FFMI_CHECK(H % c.num_heads == 0 && c.num_heads % P == 0 && F % P == 0, FFMI_ERR_INVALID);
+    if (native_gqa && c.num_kv_heads % P != 0) {
+      ffmi_set_last_error("native_gqa: num_kv_heads is not a multiple of tp_size (the replicated "
+                          "load takes this case)", __FILE__, __LINE__);
+      return FFMI_ERR_UNSUPPORTED;
+    }
     d = H / c.num_heads;
     // (d = 32: incremental decoding only, as the reference's kernels)
     FFMI_CHECK(d == 64 || d == 128 || (d == 32 && mode == FFMI_MODEL_INC), FFMI_ERR_UNSUPPORTED);
     heads_l = c.num_heads / P;
     Hl = heads_l * d;
+    kvh_l = native_gqa ? c.num_kv_heads / P : heads_l;
+    Hkv = kvh_l * d;
+    Nqkv = Hl + 2 * Hkv;
+    if (native_gqa && d != 64 && d != 128) {
+      ffmi_set_last_error("native_gqa: head_dim 64 or 128", __FILE__, __LINE__);
+      return FFMI_ERR_UNSUPPORTED;
+    }
     Fl = F / P;
     FFMI_CHECK(H % 32 == 0 && Hl % 32 == 0 && Fl % 32 == 0, FFMI_ERR_UNSUPPORTED);
     FFMI_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
     const int Tm = (o.max_tokens + 15) & ~15;  // packed tiles cover 16-row groups
     packed = H % 32 == 0 && Hl % 32 == 0 && Fl % 32 == 0;
     {
-      const double wbytes = 2.0 * c.num_layers * ((double)4 * Hl * H + 3.0 * Fl * H) +
+      const double wbytes = 2.0 * c.num_layers * (((double)Nqkv + Hl) * H + 3.0 * Fl * H) +
                             2.0 * V * H;
       wstream = wbytes > 192.0 * (1 << 20) ? FFMI_W_STREAM : 0;
       if (const char *e = getenv("FFMI_W_STREAM"))  // A/B override: 0 / 1
@@ -592,13 +617,14 @@ struct LlamaGPU : public ffmi_model {
     TRY(ffmi_batch_create(Tm, o.max_requests, &batch));
     TRY(alloc(&res, (size_t)Tm * H));
     TRY(alloc(&h, (size_t)Tm * H));
-    TRY(alloc(&qkv, (size_t)Tm * 3 * Hl));
+    TRY(alloc(&qkv, (size_t)Tm * Nqkv));
     TRY(alloc(&att, (size_t)Tm * Hl));
     TRY(alloc(&proj, (size_t)Tm * H));
     TRY(alloc(&ss_o, (size_t)2 * 32 * (H / 16)));
     ss_d = ss_o + (size_t)32 * (H / 16);
     TRY(alloc(&mlp, (size_t)Tm * Fl));
-    fuse_ao = P == 1 && d == 64 && H <= 1024 && H % 16 == 0 &&
+    // (a GQA handle does not fold the o projection in: the GEMM runs)
+    fuse_ao = !native_gqa && P == 1 && d == 64 && H <= 1024 && H % 16 == 0 &&
               !(getenv("FFMI_FUSE_AO") && atoi(getenv("FFMI_FUSE_AO")) == 0);
     if (fuse_ao) {  // decode / beam steps (<= 64 rows); prefill blocks run the GEMM
       oslab_T = std::min(Tm, 64);
@@ -641,7 +667,7 @@ struct LlamaGPU : public ffmi_model {
       // the split-K factor depends on the row-block count, so take the max
       // over every batch size the model can see
       for (int t = 16; t <= Tm; t += 16) {
-        const size_t w1 = ffmi_linear_workspace_bytes(t, 3 * Hl, H, FFMI_EPI_NONE);
+        const size_t w1 = ffmi_linear_workspace_bytes(t, Nqkv, H, FFMI_EPI_NONE);
         const size_t w2 = ffmi_linear_workspace_bytes(t, H, Hl, FFMI_EPI_NONE);
         const size_t w3 = ffmi_linear_workspace_bytes(t, Fl, H, FFMI_EPI_SILU_MUL);
         const size_t w4 = ffmi_linear_workspace_bytes(t, H, Fl, FFMI_EPI_NONE);
@@ -725,15 +751,18 @@ struct LlamaGPU : public ffmi_model {
       TRY(alloc(&L.post_norm, H));
       TRY(fill(L.post_norm, H, p + "post_attention_layernorm.weight", 1));
       // qkv: [Q_s | K_s | V_s] rows of this shard (file_loader.cc:286-303)
-      const size_t qkv_tiles_bytes = ffmi_linear_packed_bytes(Hl, H);
-      TRY(alloc(&L.wqkv, 3 * qkv_tiles_bytes / 2));
+      TRY(alloc(&L.wqkv, ffmi_linear_packed_bytes(Nqkv, H) / 2));
       const char *names[3] = {"self_attn.q_proj.weight", "self_attn.k_proj.weight",
                               "self_attn.v_proj.weight"};
       for (int q = 0; q < 3; ++q) {
-        TRY(fill(tmp, (size_t)H * H, p + names[q], 0));
-        // one allocation of 3 NT tiles per k-row: Q, K, V tiles side by side
-        FFMI_HIP(launch_pack_weight(tmp, H, s * Hl, 0, Hl, H, L.wqkv, 1, q * (Hl / 16),
-                                    3 * (Hl / 16), stream));
+        // (native GQA: the k/v tensors at their num_kv_heads * d rows, this
+        // rank's K/V heads; otherwise H rows, replicated on load if GQA)
+        const size_t rows = q > 0 && native_gqa ? (size_t)c.num_kv_heads * d : (size_t)H;
+        const int Nl = q > 0 ? Hkv : Hl;  // this rank's rows of the tensor
+        TRY(fill(tmp, rows * H, p + names[q], 0));
+        // one allocation of Nqkv / 16 tiles per k-row: Q, K, V tiles side by side
+        FFMI_HIP(launch_pack_weight(tmp, H, s * Nl, 0, Nl, H, L.wqkv, 1,
+                                    (q > 0 ? Hl + (q - 1) * Hkv : 0) / 16, Nqkv / 16, stream));
       }
       // o_proj: row-parallel -> columns [s*Hl, (s+1)*Hl)
       TRY(alloc(&L.wo, ffmi_linear_packed_bytes(H, Hl) / 2));
@@ -768,7 +797,7 @@ struct LlamaGPU : public ffmi_model {
       ac.rope_high_freq_factor = c.rope_high_freq_factor;
       ac.rope_original_max_pos = c.rope_original_max_pos;
       ac.out_layout = packed ? 1 : 0;
-      TRY(ffmi_attn_create(&ac, &L.attn));
+      TRY(ffmi_attn_create_gqa(&ac, kvh_l, &L.attn));  // (kvh_l == heads_l: ffmi_attn_create)
       int sl = 0;
       ffmi_attn_kv_ptrs(L.attn, nullptr, nullptr, &sl);
       slots = sl;
@@ -1200,10 +1229,11 @@ struct LlamaGPU : public ffmi_model {
       }
       pr = prof_begin(on);
       ffmi::Partials qkv_part;
-      FFMI_HIP(ffmi::launch_gemm(fz_in ? res : h, L.wqkv, qkv, (float *)ws, ws_bytes, T, 3 * Hl, H,
-                                 fz_in ? wstream : XP, stream, &qkv_part, 0,
+      // (a GQA handle takes fp16 qkv rows: a split-K plan runs its reduce pass)
+      FFMI_HIP(ffmi::launch_gemm(fz_in ? res : h, L.wqkv, qkv, (float *)ws, ws_bytes, T, Nqkv, H,
+                                 fz_in ? wstream : XP, stream, native_gqa ? nullptr : &qkv_part, 0,
                                  fz_in ? &fz_qkv : nullptr));
-      prof_end(pr, GEMM_QKV, gemm_bytes(T, 3 * Hl, 3 * Hl, H), 2.0 * T * 3 * Hl * H);
+      prof_end(pr, GEMM_QKV, gemm_bytes(T, Nqkv, Nqkv, H), 2.0 * T * Nqkv * H);
       mk();
       if (dbg) TRY(dbg_gemm_out(FFMI_DBG_QKV, l, qkv, qkv_part, T));
       pr = prof_begin(on);
@@ -1518,7 +1548,7 @@ struct LlamaGPU : public ffmi_model {
 }  // namespace
 
 ffmi_status create_llama_gpu(const ffmi_llama_config *cfg, const ffmi_model_opts *o,
-                             ffmi_model **out) {
+                             ffmi_model **out, unsigned flags) {
   FFMI_CHECK(cfg && o && out, FFMI_ERR_INVALID);
   FFMI_CHECK(o->tp_size >= 1 && o->tp_rank >= 0 && o->tp_rank < o->tp_size, FFMI_ERR_INVALID);
   FFMI_CHECK(o->tp_size == 1 || o->comm, FFMI_ERR_INVALID);
@@ -1531,6 +1561,7 @@ ffmi_status create_llama_gpu(const ffmi_llama_config *cfg, const ffmi_model_opts
   m->mode = o->mode;
   m->c = *cfg;
   m->o = *o;
+  m->native_gqa = (flags & FFMI_MODEL_NATIVE_GQA) != 0;
   if (o->weights_folder && o->weights_folder[0]) m->weights_folder = o->weights_folder;
   m->o.weights_folder = nullptr;
   ffmi_status st = m->init();

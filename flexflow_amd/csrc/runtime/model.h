@@ -135,6 +135,8 @@ struct ffmi_model {
     (void)arg;
     return FFMI_ERR_UNSUPPORTED;
   }
+  // bytes of the K plus V caches of every layer's attention handle
+  virtual size_t kv_cache_bytes() const { return 0; }
   virtual long debug_width(int which) const {
     (void)which;
     return -1;
@@ -143,7 +145,7 @@ struct ffmi_model {
 
 namespace ffmi {
 ffmi_status create_llama_gpu(const ffmi_llama_config *cfg, const ffmi_model_opts *o,
-                             ffmi_model **out);
+                             ffmi_model **out, unsigned flags = 0);  // (FFMI_MODEL_* bits)
 // full precision (--use-full-precision): runtime/llama_f32.cpp
 ffmi_status create_llama_f32(const ffmi_llama_config *cfg, const ffmi_model_opts *o,
                              ffmi_model **out);

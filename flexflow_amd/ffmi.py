@@ -35,6 +35,10 @@ WEIGHT_INITS = {"uniform": 0, "depth_scaled": 1, "token_chain": 2}
 FAULT_NONE, FAULT_ROPE_POS, FAULT_RESID_ROUND, FAULT_TP_HEAD_SWAP, FAULT_TP_AR_DROP = 0, 1, 2, 3, 4
 # flagged SpecInfer extensions (include/ffmi.h FFMI_SPEC_EXT_*)
 SPEC_EXT_WIDTH4, SPEC_EXT_MULTI_SSM = 1, 2
+# ffmi_model_create_ex flags (include/ffmi.h FFMI_MODEL_*)
+MODEL_NATIVE_GQA = 1
+# ffmi_attn_set_gqa_route
+GQA_ROUTE_AUTO, GQA_ROUTE_KV_INDEXED, GQA_ROUTE_GROUP_SHARED = 0, 1, 2
 ATTN_QTILE = 32
 MAX_TREE = 64
 
@@ -131,6 +135,9 @@ SIGNATURES = {
     "ffmi_batch_destroy": (None, [c_void_p]),
     "ffmi_batch_upload": (c_int, [c_void_p, ctypes.POINTER(BatchDesc), c_void_p]),
     "ffmi_attn_create": (c_int, [ctypes.POINTER(AttnCfg), ctypes.POINTER(c_void_p)]),
+    "ffmi_attn_create_gqa": (c_int, [ctypes.POINTER(AttnCfg), c_int, ctypes.POINTER(c_void_p)]),
+    "ffmi_attn_cache_bytes": (c_size_t, [c_void_p]),
+    "ffmi_attn_set_gqa_route": (c_int, [c_void_p, c_int]),
     "ffmi_attn_destroy": (None, [c_void_p]),
     "ffmi_attn_inc": (c_int, [c_void_p] * 5),
     "ffmi_attn_spec": (c_int, [c_void_p] * 5),
@@ -183,6 +190,9 @@ SIGNATURES = {
                                  c_void_p, c_void_p, c_size_t, c_void_p]),
     "ffmi_sampling_counter": (ctypes.c_uint32, [c_uint64, c_int64, c_int]),
     "ffmi_fill_weight": (c_int, [c_void_p, c_size_t, ctypes.c_char_p, c_uint64, c_int, c_void_p]),
+    "ffmi_model_create_ex": (c_int, [ctypes.POINTER(LlamaConfig), ctypes.POINTER(ModelOpts),
+                                     ctypes.c_uint, ctypes.POINTER(c_void_p)]),
+    "ffmi_model_kv_cache_bytes": (c_size_t, [c_void_p]),
     "ffmi_model_create": (c_int, [ctypes.POINTER(LlamaConfig), ctypes.POINTER(ModelOpts),
                                   ctypes.POINTER(c_void_p)]),
     "ffmi_model_destroy": (None, [c_void_p]),
@@ -298,6 +308,25 @@ def check(st, what=""):
     if st != FFMI_OK:
         msg = lib().ffmi_last_error().decode(errors="replace")
         raise FFMIError(f"{what}: {STATUS.get(st, st)} [{msg}]")
+
+
+def attn_create_gqa(cfg: "AttnCfg", num_kv_heads: int) -> c_void_p:
+    """ffmi_attn_create_gqa: an attention handle whose K/V, caches and staging
+    rows have num_kv_heads heads (query head h attends K/V head h // G)."""
+    h = c_void_p()
+    check(lib().ffmi_attn_create_gqa(ctypes.byref(cfg), num_kv_heads, ctypes.byref(h)),
+          "ffmi_attn_create_gqa")
+    return h
+
+
+def attn_cache_bytes(handle) -> int:
+    """ffmi_attn_cache_bytes: bytes of the handle's K plus V caches."""
+    return int(lib().ffmi_attn_cache_bytes(handle))
+
+
+def attn_set_gqa_route(handle, route: int) -> None:
+    """ffmi_attn_set_gqa_route: GQA_ROUTE_AUTO / _KV_INDEXED / _GROUP_SHARED."""
+    check(lib().ffmi_attn_set_gqa_route(handle, route), "ffmi_attn_set_gqa_route")
 
 
 def sampling_counter(seed: int, guid: int, pos: int) -> int:

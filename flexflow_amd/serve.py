@@ -35,14 +35,17 @@ class Model:
                  max_seq_len=512, max_tree_tokens=23, weight_seed=20250117, tp_rank=0,
                  tp_size=1, comm=None, weights_folder: Optional[str] = None,
                  weight_init: Union[int, str] = 0, full_precision: bool = False,
-                 generation_config: Optional[GenerationConfig] = None, sampling_seed: int = 0):
+                 generation_config: Optional[GenerationConfig] = None, sampling_seed: int = 0,
+                 native_gqa: bool = False):
         """weights_folder: a checkpoint in the reference's per-tensor format
         (see checkpoint.convert_hf_model); None: seeded synthetic weights,
         `weight_init` "uniform" (0, the bench's), "depth_scaled" (1) or
         "token_chain" (2) -- include/ffmi.h ffmi_model_opts.  full_precision:
         the reference's --use-full-precision (every tensor fp32,
         runtime/llama_f32.cpp); default the fp16 model.  generation_config:
-        see set_sampling (None: greedy decoding)."""
+        see set_sampling (None: greedy decoding).  native_gqa: K/V projections
+        and the KV cache at num_kv_heads instead of replicated to every query
+        head (FFMI_MODEL_NATIVE_GQA; fp16, num_kv_heads % tp_size == 0)."""
         L = F.lib()
         self.config = dict(config)
         self.mode = mode
@@ -52,7 +55,8 @@ class Model:
                            weights_folder.encode() if weights_folder else None,
                            F.WEIGHT_INITS.get(weight_init, weight_init), int(full_precision))
         h = ctypes.c_void_p()
-        F.check(L.ffmi_model_create(ctypes.byref(cfg), ctypes.byref(opts), ctypes.byref(h)),
+        F.check(L.ffmi_model_create_ex(ctypes.byref(cfg), ctypes.byref(opts),
+                                       F.MODEL_NATIVE_GQA if native_gqa else 0, ctypes.byref(h)),
                 "ffmi_model_create")
         self.handle = h
         if generation_config is not None:
@@ -114,6 +118,10 @@ class Model:
         makes `layer`'s RoPE rotate positions >= arg as position + 1;
         F.FAULT_NONE clears every fault (include/ffmi.h)."""
         F.check(F.lib().ffmi_model_debug_fault(self.handle, kind, layer, arg), "debug_fault")
+
+    def kv_cache_bytes(self) -> int:
+        """Bytes of the K plus V caches of all layers (ffmi_model_kv_cache_bytes)."""
+        return int(F.lib().ffmi_model_kv_cache_bytes(self.handle))
 
     def close(self):
         if getattr(self, "handle", None):

@@ -149,8 +149,29 @@ ffmi_status ffmi_attn_tree(ffmi_attn *h, const ffmi_batch_dev *b, const void *qk
                            void *out, ffmi_stream stream);
 /* test hooks: raw KV cache pointers and layout ([req][head][slot][d] for K,
  * [req][head][d][slot] for V -- full precision: [req][head][slot][d] for
- * both, fp32 -- slots = max_seq_len + max_tree_tokens rounded up to 32) */
+ * both, fp32 -- slots = max_seq_len + max_tree_tokens rounded up to 32).
+ * A GQA handle (ffmi_attn_create_gqa): `head` runs over its num_kv_heads. */
 ffmi_status ffmi_attn_kv_ptrs(ffmi_attn *h, void **k, void **v, int *slots);
+
+/* Native grouped-query attention (an extension: the reference replicates each
+ * K/V head to its query heads, file_loader.cc:292-302).  Query head h attends
+ * K/V head h / G, G = cfg->num_heads / num_kv_heads (HF repeat_kv).  The
+ * handle's qkv rows are [num_heads d | num_kv_heads d | num_kv_heads d], its
+ * caches K[req][kv_head][slot][d] and V^T[req][kv_head][d][slot], its TREE
+ * staging rows 2 num_kv_heads d values; ffmi_attn_inc / _spec / _tree take it
+ * as they take any handle (q, out: [T][num_heads d]).  fp16, head_dim 64 / 128.
+ * num_kv_heads <= 0 or == num_heads: ffmi_attn_create.  Not a divisor of
+ * num_heads: FFMI_ERR_INVALID.  cfg->full_precision (or head_dim 32) with
+ * G > 1: FFMI_ERR_UNSUPPORTED ("native gqa" in ffmi_last_error).  These are
+ * decided before the device is touched. */
+ffmi_status ffmi_attn_create_gqa(const ffmi_attn_cfg *cfg, int num_kv_heads, ffmi_attn **out);
+/* bytes of the handle's K plus V caches */
+size_t ffmi_attn_cache_bytes(ffmi_attn *h);
+/* test and A/B hook of a GQA handle: 0 auto, 1 kv-indexed (one workgroup per
+ * item and query head, each reading K/V head h / G), 2 group-shared wherever
+ * eligible (one workgroup per item and K/V head, every item's queries x G <=
+ * 16).  The routes give the same bits.  No effect on an MHA handle. */
+ffmi_status ffmi_attn_set_gqa_route(ffmi_attn *h, int route);
 
 /* ------------------------------------------------------------------------ */
 /* Linear (replaces Kernels::Linear::inference_kernel_wrapper,               */
@@ -447,7 +468,8 @@ typedef struct {
    * tensor, named as the HF parameter without "model." ("embed_tokens.weight",
    * "layers.0.self_attn.q_proj.weight", ..., "norm.weight", "lm_head.weight").
    * K/V projections of GQA checkpoints are replicated to every query head as
-   * the reference does (file_loader.cc:292-302).  NULL: synthetic weights. */
+   * the reference does (file_loader.cc:292-302), unless the model is created
+   * with FFMI_MODEL_NATIVE_GQA (ffmi_model_create_ex).  NULL: synthetic weights. */
   const char *weights_folder;
   /* synthetic weights (no weights_folder), oracle.h orc_model_create_ex:
    * 0: every matrix uniform with std 0.02 (the bench's model);
@@ -468,6 +490,19 @@ typedef struct {
 typedef struct ffmi_model ffmi_model;
 ffmi_status ffmi_model_create(const ffmi_llama_config *cfg, const ffmi_model_opts *o,
                               ffmi_model **out);
+/* flags: FFMI_MODEL_* bits; 0 is ffmi_model_create.
+ *   FFMI_MODEL_NATIVE_GQA: K/V projections, the qkv GEMM and the KV cache at
+ *   num_key_value_heads (ffmi_attn_create_gqa) instead of replicated to every
+ *   query head: wqkv has (num_heads + 2 num_kv_heads) d / tp_size rows per
+ *   rank, each rank its own K/V heads.  fp16 only (full_precision:
+ *   FFMI_ERR_UNSUPPORTED); num_kv_heads % tp_size != 0: FFMI_ERR_UNSUPPORTED
+ *   ("native_gqa" in ffmi_last_error) -- the replicated load takes that case.
+ *   Synthetic weights may have num_kv_heads < num_heads under the flag. */
+#define FFMI_MODEL_NATIVE_GQA 1u
+ffmi_status ffmi_model_create_ex(const ffmi_llama_config *cfg, const ffmi_model_opts *o,
+                                 unsigned flags, ffmi_model **out);
+/* bytes of the K plus V caches of all layers (this rank's; fp16 models) */
+size_t ffmi_model_kv_cache_bytes(ffmi_model *m);
 void ffmi_model_destroy(ffmi_model *m);
 /* Per-op device timing with HIP events on the model's stream (the
  * reference's --profiling, model.cc:4548-4550).  level 0: off; 1: sampled
