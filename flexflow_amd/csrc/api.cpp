@@ -258,38 +258,43 @@ struct ffmi_attn {
 };
 static_assert(offsetof(ffmi_attn, cfg) == 0, "ffmi_attn starts with its cfg (test_partials_cpu.py)");
 
-// cos/sin table, same arithmetic as the reference's apply_rotary_embedding_hf
-// (inc_multihead_self_attention.cu:701-725): freq = pos * (1.0 /
-// pow(theta, 2i/d)) in the float/double mix used there, the llama3 scaling
-// branch in f32 (its wavelength is taken of pos * inv_freq, as there), and
-// cos/sin in f32.
+// cos/sin table: freq = pos * (1.0 / pow(theta, 2i/d)) in the float/double
+// mix of the reference's apply_rotary_embedding_hf
+// (inc_multihead_self_attention.cu:701-703), cos/sin in f32.  llama3 scaling
+// in f32 as HF transformers and the Llama-3 release define it: the band is
+// chosen per frequency pair from the wavelength 2*pi / inv_freq, and the
+// scaled inv_freq then multiplies the position.  (The reference, :704-722,
+// takes the wavelength of pos * inv_freq, so its band moves with the position;
+// HF logits of a llama3-scaled model reject that at rtol 1e-4.)
 static void rope_table(std::vector<float> &tab, int max_pos, int d, const ffmi_attn_cfg *cfg) {
   const int h = d / 2;
   std::vector<double> inv(h);
-  for (int i = 0; i < h; ++i) {
-    volatile float ex = (float)2 * (float)i / (float)d;
-    inv[i] = 1.0 / (double)powf(cfg->rope_theta, ex);
-  }
   const bool l3 = cfg->rope_llama3 != 0;
   const float pi = 3.141592654f;  // CUDART_PI_F
   const float low_wl = l3 ? (float)cfg->rope_original_max_pos / cfg->rope_low_freq_factor : 0.f;
   const float high_wl = l3 ? (float)cfg->rope_original_max_pos / cfg->rope_high_freq_factor : 0.f;
+  for (int i = 0; i < h; ++i) {
+    volatile float ex = (float)2 * (float)i / (float)d;
+    inv[i] = 1.0 / (double)powf(cfg->rope_theta, ex);
+    if (l3) {
+      volatile float f = (float)inv[i];
+      const float wavelen = 2 * pi / f;
+      if (wavelen < high_wl) continue;  // short wavelengths: untouched, bit for bit
+      if (wavelen > low_wl) {
+        f = f / cfg->rope_factor;
+      } else {
+        const float smooth = ((float)cfg->rope_original_max_pos / wavelen -
+                              cfg->rope_low_freq_factor) /
+                             (cfg->rope_high_freq_factor - cfg->rope_low_freq_factor);
+        f = (1 - smooth) * f / cfg->rope_factor + smooth * f;
+      }
+      inv[i] = (double)f;
+    }
+  }
   tab.resize((size_t)max_pos * d);
   for (int p = 0; p < max_pos; ++p)
     for (int i = 0; i < h; ++i) {
       volatile float freq = (float)((double)p * inv[i]);
-      if (l3) {
-        const float wavelen = 2 * pi / freq;
-        if (wavelen < high_wl) {
-        } else if (wavelen > low_wl) {
-          freq = freq / cfg->rope_factor;
-        } else {
-          const float smooth = ((float)cfg->rope_original_max_pos / wavelen -
-                                cfg->rope_low_freq_factor) /
-                               (cfg->rope_high_freq_factor - cfg->rope_low_freq_factor);
-          freq = (1 - smooth) * freq / cfg->rope_factor + smooth * freq;
-        }
-      }
       tab[((size_t)p * h + i) * 2 + 0] = cosf(freq);
       tab[((size_t)p * h + i) * 2 + 1] = sinf(freq);
     }

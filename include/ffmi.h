@@ -121,8 +121,10 @@ typedef struct {
   int out_layout;      /* 0: out [T][heads*head_dim] row-major;
                           1: packed activation tiles (feeds ffmi_linear with
                           FFMI_X_PACKED; heads*head_dim % 32 == 0)          */
-  /* llama3 RoPE frequency scaling (inc_multihead_self_attention.cu:703-722;
-   * rope_llama3 = 0: plain HF RoPE, the other fields ignored)               */
+  /* llama3 RoPE frequency scaling as HF transformers defines it: the band of
+   * a frequency pair from its wavelength 2*pi / inv_freq (the reference's
+   * inc_multihead_self_attention.cu:704-722 takes it of pos * inv_freq);
+   * rope_llama3 = 0: plain HF RoPE, the other fields ignored               */
   int rope_llama3;
   float rope_factor, rope_low_freq_factor, rope_high_freq_factor;
   int rope_original_max_pos;

@@ -394,33 +394,40 @@ extern "C" void orc_silu_mul(const float *A, const float *B, float *out,
 }
 
 // RoPE table: freq = pos * (1.0 / pow(theta, 2i/d)) with the reference's
-// float/double mix (inc_multihead_self_attention.cu:701-703), the llama3
-// scaling branch in f32 (:704-722: its wavelength is 2*pi / freq of the
-// already position-scaled freq), cos/sin in f32.
+// float/double mix (inc_multihead_self_attention.cu:701-703), cos/sin in f32.
+// llama3 scaling in f32 as HF transformers (_compute_llama3_parameters) and
+// the Llama-3 release define it: the band is chosen per frequency pair from
+// the wavelength 2*pi / inv_freq, and the scaled inv_freq then multiplies the
+// position.  The reference (:704-722) takes the wavelength of the already
+// position-scaled freq, so its band moves with the position (and every pair
+// of position 0..1 is "long"): a deviation from the model's definition that
+// the HF fixture tests/golden/tiny_gqa_d128_llama3 rejects at rtol 1e-4.
 extern "C" void orc_rope_table_llama3(float *tab, int max_pos, int d, float theta, int llama3,
                                       float factor, float low_ff, float high_ff, int orig_max) {
   const int h = d / 2;
   std::vector<double> inv(h);
-  for (int i = 0; i < h; ++i) {
-    float ex = (float)2 * (float)i / (float)d;
-    inv[i] = 1.0 / (double)powf(theta, ex);
-  }
   const float pi = 3.141592654f;
   const float low_wl = llama3 ? (float)orig_max / low_ff : 0.f;
   const float high_wl = llama3 ? (float)orig_max / high_ff : 0.f;
+  for (int i = 0; i < h; ++i) {
+    float ex = (float)2 * (float)i / (float)d;
+    inv[i] = 1.0 / (double)powf(theta, ex);
+    if (llama3) {
+      float f = (float)inv[i];
+      const float wavelen = 2 * pi / f;
+      if (wavelen < high_wl) continue;  // short wavelengths: untouched, bit for bit
+      if (wavelen > low_wl) {
+        f = f / factor;
+      } else {
+        const float smooth = ((float)orig_max / wavelen - low_ff) / (high_ff - low_ff);
+        f = (1 - smooth) * f / factor + smooth * f;
+      }
+      inv[i] = (double)f;
+    }
+  }
   for (int p = 0; p < max_pos; ++p)
     for (int i = 0; i < h; ++i) {
       float freq = (float)((double)p * inv[i]);
-      if (llama3) {
-        float wavelen = 2 * pi / freq;
-        if (wavelen < high_wl) {
-        } else if (wavelen > low_wl) {
-          freq = freq / factor;
-        } else {
-          float smooth = ((float)orig_max / wavelen - low_ff) / (high_ff - low_ff);
-          freq = (1 - smooth) * freq / factor + smooth * freq;
-        }
-      }
       tab[((size_t)p * h + i) * 2 + 0] = cosf(freq);
       tab[((size_t)p * h + i) * 2 + 1] = sinf(freq);
     }
@@ -600,7 +607,7 @@ struct orc_model {
     fvec in_norm, post_norm, wq, wk, wv, wo, wg, wu, wd;
   };
   std::vector<Layer> layers;
-  std::vector<float> kc, vc;  // [req][layer][pos][H]
+  std::vector<float> kc, vc;  // [req][layer][pos][Hkv], Hkv = num_kv_heads * d
   std::vector<float> rope;    // [max_seq][d/2][2]
   std::vector<std::vector<float>> hidden;  // debug: per-layer output of last call
   // per-op tensors of the last orc_model_forward_ex call, by FFMI_DBG_* kind
@@ -643,7 +650,7 @@ extern "C" float orc_chain_embed_scale(int num_layers, int hidden, int intermedi
 
 extern "C" orc_model *orc_model_create_ex(const orc_config *cfg, uint64_t seed, int fp16,
                                           int max_requests, int max_seq, int weight_init) {
-  if (cfg->num_kv_heads != cfg->num_heads) return nullptr;  // MHA only
+  if (cfg->num_kv_heads <= 0 || cfg->num_heads % cfg->num_kv_heads) return nullptr;
   orc_model *m = new orc_model();
   m->c = *cfg;
   m->fp16 = fp16;
@@ -651,6 +658,7 @@ extern "C" orc_model *orc_model_create_ex(const orc_config *cfg, uint64_t seed, 
   m->max_seq = max_seq;
   m->d = cfg->hidden / cfg->num_heads;
   const size_t H = cfg->hidden, F = cfg->intermediate, Vv = cfg->vocab_size;
+  const size_t Hkv = (size_t)cfg->num_kv_heads * m->d;  // K/V width (== H for MHA)
   if (weight_init == 2) {
     // token-chain init: embeddings x orc_chain_embed_scale, lm_head row v =
     // the unscaled embedding row of perm(v) (a tied, permuted head): the
@@ -671,8 +679,8 @@ extern "C" orc_model *orc_model_create_ex(const orc_config *cfg, uint64_t seed, 
     gen(L.in_norm, p + "input_layernorm.weight", seed, 1, H, fp16);
     gen(L.post_norm, p + "post_attention_layernorm.weight", seed, 1, H, fp16);
     gen(L.wq, p + "self_attn.q_proj.weight", seed, 0, H * H, fp16);
-    gen(L.wk, p + "self_attn.k_proj.weight", seed, 0, H * H, fp16);
-    gen(L.wv, p + "self_attn.v_proj.weight", seed, 0, H * H, fp16);
+    gen(L.wk, p + "self_attn.k_proj.weight", seed, 0, Hkv * H, fp16);
+    gen(L.wv, p + "self_attn.v_proj.weight", seed, 0, Hkv * H, fp16);
     // depth-scaled init: the residual-branch outputs at 1/sqrt(2L)
     const int kres = weight_init == 1 ? (ORC_WKIND_DEPTH | cfg->num_layers) : 0;
     gen(L.wo, p + "self_attn.o_proj.weight", seed, kres, H * H, fp16);
@@ -680,12 +688,18 @@ extern "C" orc_model *orc_model_create_ex(const orc_config *cfg, uint64_t seed, 
     gen(L.wu, p + "mlp.up_proj.weight", seed, 0, F * H, fp16);
     gen(L.wd, p + "mlp.down_proj.weight", seed, kres, H * F, fp16);
   }
-  m->kc.assign((size_t)max_requests * cfg->num_layers * max_seq * H, 0.f);
-  m->vc.assign((size_t)max_requests * cfg->num_layers * max_seq * H, 0.f);
+  m->kc.assign((size_t)max_requests * cfg->num_layers * max_seq * Hkv, 0.f);
+  m->vc.assign((size_t)max_requests * cfg->num_layers * max_seq * Hkv, 0.f);
   m->rope.resize((size_t)max_seq * m->d);
   orc_rope_table(m->rope.data(), max_seq, m->d, cfg->rope_theta);
   m->hidden.resize(cfg->num_layers + 1);
   return m;
+}
+
+extern "C" void orc_model_set_rope_llama3(orc_model *m, float factor, float low_ff,
+                                          float high_ff, int orig_max) {
+  orc_rope_table_llama3(m->rope.data(), m->max_seq, m->d, m->c.rope_theta, 1, factor, low_ff,
+                        high_ff, orig_max);
 }
 
 extern "C" void orc_model_destroy(orc_model *m) { delete m; }
@@ -736,10 +750,13 @@ extern "C" int orc_model_forward_ex(orc_model *m, int req, const int *tokens, in
                                     int start_pos, float *logits, int prompt_phase) {
   const orc_config &c = m->c;
   const int H = c.hidden, F = c.intermediate, d = m->d, nh = c.num_heads;
+  // grouped-query attention: nkv K/V heads, query head hd reads K/V head hd / G
+  // (HF repeat_kv); G == 1 is multi-head attention, Hkv == H
+  const int nkv = c.num_kv_heads, G = nh / nkv, Hkv = nkv * d;
   const int fp16 = m->fp16;
   if (req < 0 || req >= m->max_requests || start_pos + T > m->max_seq) return -1;
   std::vector<float> x((size_t)T * H), h((size_t)T * H), res((size_t)T * H);
-  std::vector<float> q((size_t)T * H), k((size_t)T * H), v((size_t)T * H);
+  std::vector<float> q((size_t)T * H), k((size_t)T * Hkv), v((size_t)T * Hkv);
   std::vector<float> att((size_t)T * H), o((size_t)T * H), mlp((size_t)T * H);
   std::vector<float> g((size_t)T * F), u((size_t)T * F), a((size_t)T * F);
   for (int t = 0; t < T; ++t)
@@ -760,33 +777,33 @@ extern "C" int orc_model_forward_ex(orc_model *m, int req, const int *tokens, in
     }
     keep_op(m, 2, l, h.data(), h.size());
     orc_linear(h.data(), L.wq.data(), q.data(), T, H, H, fp16);
-    orc_linear(h.data(), L.wk.data(), k.data(), T, H, H, fp16);
-    orc_linear(h.data(), L.wv.data(), v.data(), T, H, H, fp16);
+    orc_linear(h.data(), L.wk.data(), k.data(), T, Hkv, H, fp16);
+    orc_linear(h.data(), L.wv.data(), v.data(), T, Hkv, H, fp16);
     {
-      std::vector<float> qkv3((size_t)T * 3 * H);
+      const size_t W = (size_t)H + 2 * Hkv;
+      std::vector<float> qkv3((size_t)T * W);
       for (int t = 0; t < T; ++t) {
-        memcpy(&qkv3[(size_t)t * 3 * H], &q[(size_t)t * H], H * sizeof(float));
-        memcpy(&qkv3[(size_t)t * 3 * H + H], &k[(size_t)t * H], H * sizeof(float));
-        memcpy(&qkv3[(size_t)t * 3 * H + 2 * H], &v[(size_t)t * H], H * sizeof(float));
+        memcpy(&qkv3[(size_t)t * W], &q[(size_t)t * H], H * sizeof(float));
+        memcpy(&qkv3[(size_t)t * W + H], &k[(size_t)t * Hkv], Hkv * sizeof(float));
+        memcpy(&qkv3[(size_t)t * W + H + Hkv], &v[(size_t)t * Hkv], Hkv * sizeof(float));
       }
       keep_op(m, 3, l, qkv3.data(), qkv3.size());
     }
-    float *kc = &m->kc[(((size_t)req * c.num_layers + l) * m->max_seq) * H];
-    float *vc = &m->vc[(((size_t)req * c.num_layers + l) * m->max_seq) * H];
+    float *kc = &m->kc[(((size_t)req * c.num_layers + l) * m->max_seq) * Hkv];
+    float *vc = &m->vc[(((size_t)req * c.num_layers + l) * m->max_seq) * Hkv];
     for (int t = 0; t < T; ++t) {
       int pos = start_pos + t;
       for (int hd = 0; hd < nh; ++hd) {
         float *qh = &q[(size_t)t * H + hd * d];
-        float *kh = &k[(size_t)t * H + hd * d];
         rope_apply(qh, d, &m->rope[(size_t)pos * d]);
+        for (int i = 0; i < d; ++i) qh[i] = R(qh[i], fp16);
+        if (hd >= nkv) continue;
+        float *kh = &k[(size_t)t * Hkv + hd * d];
         rope_apply(kh, d, &m->rope[(size_t)pos * d]);
-        for (int i = 0; i < d; ++i) {
-          qh[i] = R(qh[i], fp16);
-          kh[i] = R(kh[i], fp16);
-        }
+        for (int i = 0; i < d; ++i) kh[i] = R(kh[i], fp16);
       }
-      memcpy(kc + (size_t)pos * H, &k[(size_t)t * H], H * sizeof(float));
-      memcpy(vc + (size_t)pos * H, &v[(size_t)t * H], H * sizeof(float));
+      memcpy(kc + (size_t)pos * Hkv, &k[(size_t)t * Hkv], Hkv * sizeof(float));
+      memcpy(vc + (size_t)pos * Hkv, &v[(size_t)t * Hkv], Hkv * sizeof(float));
     }
     const int nk = start_pos + T;
 #pragma omp parallel
@@ -796,8 +813,8 @@ extern "C" int orc_model_forward_ex(orc_model *m, int req, const int *tokens, in
 #pragma omp for schedule(static)
       for (int hd = 0; hd < nh; ++hd) {
         for (int j = 0; j < nk; ++j) {
-          memcpy(&Kh[(size_t)j * d], kc + (size_t)j * H + hd * d, d * sizeof(float));
-          memcpy(&Vh[(size_t)j * d], vc + (size_t)j * H + hd * d, d * sizeof(float));
+          memcpy(&Kh[(size_t)j * d], kc + (size_t)j * Hkv + (hd / G) * d, d * sizeof(float));
+          memcpy(&Vh[(size_t)j * d], vc + (size_t)j * Hkv + (hd / G) * d, d * sizeof(float));
         }
         if (prompt_phase && fp16 == ORC_REF16) {
           std::vector<float> qh((size_t)T * d), oh((size_t)T * d);
@@ -850,11 +867,14 @@ extern "C" int orc_model_decode_batch(orc_model *m, const int *reqs, const int *
                                       const int *pos, int T, float *logits) {
   const orc_config &c = m->c;
   const int H = c.hidden, F = c.intermediate, d = m->d, nh = c.num_heads;
+  // grouped-query attention: nkv K/V heads, query head hd reads K/V head hd / G
+  // (HF repeat_kv); G == 1 is multi-head attention, Hkv == H
+  const int nkv = c.num_kv_heads, G = nh / nkv, Hkv = nkv * d;
   const int fp16 = m->fp16;
   for (int t = 0; t < T; ++t)
     if (reqs[t] < 0 || reqs[t] >= m->max_requests || pos[t] >= m->max_seq) return -1;
   std::vector<float> res((size_t)T * H), h((size_t)T * H), r2((size_t)T * H);
-  std::vector<float> q((size_t)T * H), k((size_t)T * H), v((size_t)T * H);
+  std::vector<float> q((size_t)T * H), k((size_t)T * Hkv), v((size_t)T * Hkv);
   std::vector<float> att((size_t)T * H), o((size_t)T * H), mlp((size_t)T * H);
   std::vector<float> g((size_t)T * F), u((size_t)T * F), a((size_t)T * F);
   for (int t = 0; t < T; ++t)
@@ -870,31 +890,30 @@ extern "C" int orc_model_decode_batch(orc_model *m, const int *reqs, const int *
       res.swap(r2);
     }
     orc_linear(h.data(), L.wq.data(), q.data(), T, H, H, fp16);
-    orc_linear(h.data(), L.wk.data(), k.data(), T, H, H, fp16);
-    orc_linear(h.data(), L.wv.data(), v.data(), T, H, H, fp16);
+    orc_linear(h.data(), L.wk.data(), k.data(), T, Hkv, H, fp16);
+    orc_linear(h.data(), L.wv.data(), v.data(), T, Hkv, H, fp16);
 #pragma omp parallel for schedule(static)
     for (int t = 0; t < T; ++t) {
       const int req = reqs[t], p = pos[t];
-      float *kc = &m->kc[(((size_t)req * c.num_layers + l) * m->max_seq) * H];
-      float *vc = &m->vc[(((size_t)req * c.num_layers + l) * m->max_seq) * H];
+      float *kc = &m->kc[(((size_t)req * c.num_layers + l) * m->max_seq) * Hkv];
+      float *vc = &m->vc[(((size_t)req * c.num_layers + l) * m->max_seq) * Hkv];
       for (int hd = 0; hd < nh; ++hd) {
         float *qh = &q[(size_t)t * H + hd * d];
-        float *kh = &k[(size_t)t * H + hd * d];
         rope_apply(qh, d, &m->rope[(size_t)p * d]);
+        for (int i = 0; i < d; ++i) qh[i] = R(qh[i], fp16);
+        if (hd >= nkv) continue;
+        float *kh = &k[(size_t)t * Hkv + hd * d];
         rope_apply(kh, d, &m->rope[(size_t)p * d]);
-        for (int i = 0; i < d; ++i) {
-          qh[i] = R(qh[i], fp16);
-          kh[i] = R(kh[i], fp16);
-        }
+        for (int i = 0; i < d; ++i) kh[i] = R(kh[i], fp16);
       }
-      memcpy(kc + (size_t)p * H, &k[(size_t)t * H], H * sizeof(float));
-      memcpy(vc + (size_t)p * H, &v[(size_t)t * H], H * sizeof(float));
+      memcpy(kc + (size_t)p * Hkv, &k[(size_t)t * Hkv], Hkv * sizeof(float));
+      memcpy(vc + (size_t)p * Hkv, &v[(size_t)t * Hkv], Hkv * sizeof(float));
       std::vector<float> Kh((size_t)(p + 1) * d), Vh((size_t)(p + 1) * d);
       std::vector<uint8_t> vis(p + 1, 1);
       for (int hd = 0; hd < nh; ++hd) {
         for (int j = 0; j <= p; ++j) {
-          memcpy(&Kh[(size_t)j * d], kc + (size_t)j * H + hd * d, d * sizeof(float));
-          memcpy(&Vh[(size_t)j * d], vc + (size_t)j * H + hd * d, d * sizeof(float));
+          memcpy(&Kh[(size_t)j * d], kc + (size_t)j * Hkv + (hd / G) * d, d * sizeof(float));
+          memcpy(&Vh[(size_t)j * d], vc + (size_t)j * Hkv + (hd / G) * d, d * sizeof(float));
         }
         orc_attention_row(&q[(size_t)t * H + hd * d], Kh.data(), Vh.data(), vis.data(), p + 1,
                           d, scale, &att[(size_t)t * H + hd * d], fp16);
@@ -925,6 +944,9 @@ extern "C" int orc_model_forward_multi(orc_model *m, int nreq, const int *reqs, 
                                        const int *start, const int *tokens, float *logits) {
   const orc_config &c = m->c;
   const int H = c.hidden, F = c.intermediate, d = m->d, nh = c.num_heads;
+  // grouped-query attention: nkv K/V heads, query head hd reads K/V head hd / G
+  // (HF repeat_kv); G == 1 is multi-head attention, Hkv == H
+  const int nkv = c.num_kv_heads, G = nh / nkv, Hkv = nkv * d;
   const int fp16 = m->fp16;
   std::vector<int> off(nreq + 1, 0);
   for (int r = 0; r < nreq; ++r) {
@@ -935,7 +957,7 @@ extern "C" int orc_model_forward_multi(orc_model *m, int nreq, const int *reqs, 
   }
   const int T = off[nreq];
   std::vector<float> res((size_t)T * H), h((size_t)T * H), r2((size_t)T * H);
-  std::vector<float> q((size_t)T * H), k((size_t)T * H), v((size_t)T * H);
+  std::vector<float> q((size_t)T * H), k((size_t)T * Hkv), v((size_t)T * Hkv);
   std::vector<float> att((size_t)T * H), o((size_t)T * H), mlp((size_t)T * H);
   std::vector<float> g((size_t)T * F), u((size_t)T * F), a((size_t)T * F);
   for (int t = 0; t < T; ++t)
@@ -951,38 +973,37 @@ extern "C" int orc_model_forward_multi(orc_model *m, int nreq, const int *reqs, 
       res.swap(r2);
     }
     orc_linear(h.data(), L.wq.data(), q.data(), T, H, H, fp16);
-    orc_linear(h.data(), L.wk.data(), k.data(), T, H, H, fp16);
-    orc_linear(h.data(), L.wv.data(), v.data(), T, H, H, fp16);
+    orc_linear(h.data(), L.wk.data(), k.data(), T, Hkv, H, fp16);
+    orc_linear(h.data(), L.wv.data(), v.data(), T, Hkv, H, fp16);
     for (int r = 0; r < nreq; ++r) {
-      float *kc = &m->kc[(((size_t)reqs[r] * c.num_layers + l) * m->max_seq) * H];
-      float *vc = &m->vc[(((size_t)reqs[r] * c.num_layers + l) * m->max_seq) * H];
+      float *kc = &m->kc[(((size_t)reqs[r] * c.num_layers + l) * m->max_seq) * Hkv];
+      float *vc = &m->vc[(((size_t)reqs[r] * c.num_layers + l) * m->max_seq) * Hkv];
       for (int i = 0; i < counts[r]; ++i) {
         const int t = off[r] + i, pos = start[r] + i;
         for (int hd = 0; hd < nh; ++hd) {
           float *qh = &q[(size_t)t * H + hd * d];
-          float *kh = &k[(size_t)t * H + hd * d];
           rope_apply(qh, d, &m->rope[(size_t)pos * d]);
+          for (int e = 0; e < d; ++e) qh[e] = R(qh[e], fp16);
+          if (hd >= nkv) continue;
+          float *kh = &k[(size_t)t * Hkv + hd * d];
           rope_apply(kh, d, &m->rope[(size_t)pos * d]);
-          for (int e = 0; e < d; ++e) {
-            qh[e] = R(qh[e], fp16);
-            kh[e] = R(kh[e], fp16);
-          }
+          for (int e = 0; e < d; ++e) kh[e] = R(kh[e], fp16);
         }
-        memcpy(kc + (size_t)pos * H, &k[(size_t)t * H], H * sizeof(float));
-        memcpy(vc + (size_t)pos * H, &v[(size_t)t * H], H * sizeof(float));
+        memcpy(kc + (size_t)pos * Hkv, &k[(size_t)t * Hkv], Hkv * sizeof(float));
+        memcpy(vc + (size_t)pos * Hkv, &v[(size_t)t * Hkv], Hkv * sizeof(float));
       }
     }
 #pragma omp parallel for collapse(2) schedule(dynamic)
     for (int r = 0; r < nreq; ++r)
       for (int hd = 0; hd < nh; ++hd) {
-        const float *kc = &m->kc[(((size_t)reqs[r] * c.num_layers + l) * m->max_seq) * H];
-        const float *vc = &m->vc[(((size_t)reqs[r] * c.num_layers + l) * m->max_seq) * H];
+        const float *kc = &m->kc[(((size_t)reqs[r] * c.num_layers + l) * m->max_seq) * Hkv];
+        const float *vc = &m->vc[(((size_t)reqs[r] * c.num_layers + l) * m->max_seq) * Hkv];
         const int nk = start[r] + counts[r];
         std::vector<float> Kh((size_t)nk * d), Vh((size_t)nk * d);
         std::vector<uint8_t> vis(nk);
         for (int j = 0; j < nk; ++j) {
-          memcpy(&Kh[(size_t)j * d], kc + (size_t)j * H + hd * d, d * sizeof(float));
-          memcpy(&Vh[(size_t)j * d], vc + (size_t)j * H + hd * d, d * sizeof(float));
+          memcpy(&Kh[(size_t)j * d], kc + (size_t)j * Hkv + (hd / G) * d, d * sizeof(float));
+          memcpy(&Vh[(size_t)j * d], vc + (size_t)j * Hkv + (hd / G) * d, d * sizeof(float));
         }
         for (int i = 0; i < counts[r]; ++i) {
           const int t = off[r] + i, pos = start[r] + i;

@@ -138,6 +138,15 @@ orc_model *orc_model_create(const orc_config *cfg, uint64_t seed, int fp16,
  * lead by margins far above fp16 rounding noise */
 orc_model *orc_model_create_ex(const orc_config *cfg, uint64_t seed, int fp16,
                                int max_requests, int max_seq, int weight_init);
+/* grouped-query attention: num_kv_heads divides num_heads; k_proj / v_proj are
+ * [num_kv_heads * d][hidden] (drawn from the name-keyed stream at that element
+ * count), the K/V caches hold num_kv_heads heads, and query head h attends
+ * over K/V head h / (num_heads / num_kv_heads) -- HF repeat_kv.  With
+ * num_kv_heads == num_heads every value and summation order is the MHA one. */
+/* rebuild the model's RoPE table with llama3 frequency scaling
+ * (orc_rope_table_llama3 with the model's theta); orc_config keeps its layout */
+void orc_model_set_rope_llama3(orc_model *m, float factor, float low_ff, float high_ff,
+                               int orig_max);
 void orc_model_destroy(orc_model *m);
 void orc_model_reset(orc_model *m, int req);
 /* Feed T tokens of request `req` at positions start_pos..start_pos+T-1
@@ -164,8 +173,9 @@ int orc_model_forward_multi(orc_model *m, int R, const int *reqs, const int *cou
  * the last forward call, [T][H]; layer == num_layers gives final-normed. */
 int orc_model_get_hidden(orc_model *m, int layer, float *out);
 /* per-op tensor of the last forward (kind = FFMI_DBG_* of include/ffmi.h,
- * 2..9: attn_norm, qkv before RoPE [Q|K|V], attn_out, o_proj, ffn_norm,
- * mlp_act, down, embed (layer 0)); returns T or -1; out NULL: T only */
+ * 2..9: attn_norm, qkv before RoPE [Q|K|V] at width hidden + 2 * num_kv_heads
+ * * d (3 * hidden for MHA), attn_out, o_proj, ffn_norm, mlp_act, down, embed
+ * (layer 0)); returns T or -1; out NULL: T only */
 int orc_model_get_op(orc_model *m, int kind, int layer, float *out);
 /* greedy incremental decoding of one request: writes n_new tokens */
 int orc_model_greedy(orc_model *m, int req, const int *prompt, int n_prompt,

@@ -10,10 +10,11 @@ every tensor from the same counter-based splitmix64 spec (see
 oracle/oracle.h: orc_gen_weight), so a fixture is (config, seed, prompt) ->
 (greedy tokens, logits, per-layer hidden states).
 
-    python tests/golden/gen_golden.py
+    python tests/golden/gen_golden.py [tag ...]     (no tag: every config)
 """
 import json
 import os
+import sys
 
 import numpy as np
 
@@ -58,6 +59,18 @@ CONFIGS = {
     "tiny_d128": dict(num_layers=2, vocab_size=1000, num_heads=2, num_kv_heads=2,
                       hidden=256, intermediate=512, rms_eps=1e-6,
                       rope_theta=10000.0, seed=11, prompt_len=9, n_new=16),
+    # grouped-query attention, 4 query heads over 2 K/V heads: with two K/V
+    # heads the HF mapping h / G (0,0,1,1) differs from h % num_kv_heads (0,1,0,1)
+    "tiny_gqa_d64": dict(num_layers=2, vocab_size=512, num_heads=4, num_kv_heads=2,
+                         hidden=256, intermediate=512, rms_eps=1e-6,
+                         rope_theta=10000.0, seed=202, prompt_len=24, n_new=16),
+    # Llama-3 style: multi-query (G = 4), theta 5e5, llama3 RoPE scaling whose
+    # three wavelength bands are all populated at d = 128
+    "tiny_gqa_d128_llama3": dict(num_layers=2, vocab_size=500, num_heads=4, num_kv_heads=1,
+                                 hidden=512, intermediate=1024, rms_eps=1e-5,
+                                 rope_theta=500000.0, rope_llama3=1, rope_factor=8.0,
+                                 rope_low_freq_factor=1.0, rope_high_freq_factor=4.0,
+                                 rope_original_max_pos=64, seed=202, prompt_len=20, n_new=16),
 }
 
 
@@ -65,12 +78,20 @@ def build_hf(cfg):
     import torch
     from transformers import LlamaConfig, LlamaForCausalLM
 
+    if cfg.get("rope_llama3"):
+        rope = dict(rope_parameters=dict(
+            rope_type="llama3", rope_theta=cfg["rope_theta"], factor=cfg["rope_factor"],
+            low_freq_factor=cfg["rope_low_freq_factor"],
+            high_freq_factor=cfg["rope_high_freq_factor"],
+            original_max_position_embeddings=cfg["rope_original_max_pos"]))
+    else:
+        rope = dict(rope_theta=cfg["rope_theta"])
     hc = LlamaConfig(vocab_size=cfg["vocab_size"], hidden_size=cfg["hidden"],
                      intermediate_size=cfg["intermediate"],
                      num_hidden_layers=cfg["num_layers"],
                      num_attention_heads=cfg["num_heads"],
                      num_key_value_heads=cfg["num_kv_heads"],
-                     rms_norm_eps=cfg["rms_eps"], rope_theta=cfg["rope_theta"],
+                     rms_norm_eps=cfg["rms_eps"], **rope,
                      max_position_embeddings=512, tie_word_embeddings=False,
                      attention_bias=False, mlp_bias=False)
     hc._attn_implementation = "eager"
@@ -94,11 +115,12 @@ def make_prompt(cfg):
     return np.concatenate([[1], ids]).astype(np.int32)
 
 
-def main():
+def main(tags=None):
     import torch
 
     torch.manual_seed(0)
-    for tag, cfg in CONFIGS.items():
+    for tag in tags or CONFIGS:
+        cfg = CONFIGS[tag]
         model = build_hf(cfg)
         prompt = make_prompt(cfg)
         with torch.no_grad():
@@ -107,8 +129,11 @@ def main():
             logits = out.logits[0].float().numpy()
             hidden = np.stack([h[0].float().numpy() for h in out.hidden_states[1:]])
             seq = list(prompt.tolist())
+            gap = np.inf  # smallest top-2 logit gap over the greedy picks
             for _ in range(cfg["n_new"]):
                 lg = model(torch.tensor([seq])).logits[0, -1]
+                top2 = torch.topk(lg, 2).values
+                gap = min(gap, float(top2[0] - top2[1]))
                 seq.append(int(torch.argmax(lg)))
         greedy = np.array(seq[len(prompt):], dtype=np.int32)
         path = os.path.join(HERE, f"{tag}.npz")
@@ -116,8 +141,8 @@ def main():
                             prompt=prompt, greedy=greedy,
                             logits=logits.astype(np.float32),
                             hidden=hidden.astype(np.float32))
-        print(tag, "greedy:", greedy.tolist())
+        print(tag, "greedy:", greedy.tolist(), "min top-2 gap: %.4g" % gap)
 
 
 if __name__ == "__main__":
-    main()
+    main(sys.argv[1:])

@@ -68,6 +68,8 @@ def lib():
         L.orc_weight_amp.argtypes = [ctypes.c_int]
         L.orc_chain_embed_scale.restype = ctypes.c_float
         L.orc_chain_embed_scale.argtypes = [ctypes.c_int] * 3
+        L.orc_model_set_rope_llama3.argtypes = [ctypes.c_void_p, ctypes.c_float, ctypes.c_float,
+                                                ctypes.c_float, ctypes.c_int]
         L.orc_model_destroy.argtypes = [ctypes.c_void_p]
         L.orc_model_forward.argtypes = [ctypes.c_void_p, ctypes.c_int, _i32p,
                                         ctypes.c_int, ctypes.c_int, _f32p]
@@ -230,6 +232,11 @@ class Model:
         if not self.h:
             raise RuntimeError("orc_model_create failed")
         self.fp16 = fp16
+        if cfg.get("rope_llama3"):  # the keys llama_config_from_hf emits
+            lib().orc_model_set_rope_llama3(self.h, cfg["rope_factor"],
+                                            cfg["rope_low_freq_factor"],
+                                            cfg["rope_high_freq_factor"],
+                                            int(cfg["rope_original_max_pos"]))
 
     def __del__(self):
         if getattr(self, "h", None):
@@ -300,7 +307,10 @@ class Model:
         T = lib().orc_model_get_op(self.h, k, layer, None)
         assert T > 0, (which, layer)
         H, F = self.cfg["hidden"], self.cfg["intermediate"]
-        width = {3: 3 * H, 7: F}.get(k, H)
+        # qkv is [Q|K|V] with K/V at num_kv_heads heads (3 * H for MHA)
+        nh = self.cfg["num_heads"]
+        Hkv = self.cfg.get("num_kv_heads", nh) * (H // nh)
+        width = {3: H + 2 * Hkv, 7: F}.get(k, H)
         out = np.empty((T, width), np.float32)
         lib().orc_model_get_op(self.h, k, layer, fp(out))
         return out

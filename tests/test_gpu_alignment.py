@@ -28,7 +28,7 @@ from hip_util import report, ulp_diff
 
 pytestmark = pytest.mark.gpu
 
-TAGS = ["tiny_d64", "tiny_d128"]
+TAGS = ["tiny_d64", "tiny_d128", "tiny_gqa_d64", "tiny_gqa_d128_llama3"]
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -38,6 +38,8 @@ def prefill_capture(cfg, seed, prompt, mode="inc", **kw):
     """One prefill step of `prompt` (BOS first) with tensor capture; returns
     the model (captured tensors of that step)."""
     n = len(prompt)
+    if cfg.get("num_kv_heads", cfg["num_heads"]) != cfg["num_heads"]:
+        kw.setdefault("native_gqa", True)  # a seeded GQA model needs the flag
     rm = fa.RequestManager(max_requests_per_batch=1, max_tokens_per_batch=max(16, n),
                            max_sequence_length=max(64, n + 2))
     m = fa.Model(cfg, mode, max_requests=1, max_tokens=max(16, n), max_seq_len=max(64, n + 2),

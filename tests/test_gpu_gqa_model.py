@@ -3,11 +3,13 @@ K/V projections, the qkv GEMM and the KV cache at num_kv_heads).
 
 The model: 2 layers, V 1000, H 512, 8 query heads over 2 K/V heads (d 64), a
 reference-format checkpoint written with convert_hf_model as
-test_gpu_checkpoint.py writes one.  The oracle is MHA only, so the references
-here are the default load of the same checkpoint (K/V replicated to every
-query head, the reference's layout, pinned by test_gpu_checkpoint.py) and, for
-the attention alone, the oracle's attention_row on the model's own captured
-qkv.  Between the replicated and the native model only the qkv GEMM's N
+test_gpu_checkpoint.py writes one.  These tests are differential: the
+references are the default load of the same checkpoint (K/V replicated to
+every query head, the reference's layout, pinned by test_gpu_checkpoint.py)
+and, for the attention alone, the oracle's attention_row on the model's own
+captured qkv -- route equality and cache sizes, which the oracle cannot see.
+The oracle's own GQA model (HF-pinned on tests/golden/tiny_gqa_d64) checks
+this model, its TP split and SpecInfer over it in test_gpu_gqa_oracle.py.  Between the replicated and the native model only the qkv GEMM's N
 differs (1536 against 768 columns), so its launch plan -- the order of its
 fp32 sums -- may differ; every other op sees the same shapes.
 """
@@ -185,7 +187,8 @@ def test_native_attention_local_check(base):
 def test_spec_infer_under_the_flag_equals_incremental_decoding(base, ckpt, draft):
     """test_gpu_e2e.py's rule: identical, or the first divergence is a tie of
     the two tokens' fp16 probabilities within 2 ulp -- on the flagged
-    incremental model's own teacher-forced row, the oracle being MHA only.
+    incremental model's own teacher-forced row (the oracle checks every pick
+    of this configuration in test_gpu_gqa_oracle.py).
     The SSM: test_gpu_e2e.py's MHA one, or (native_same) the LLM's own
     checkpoint as a BEAM model under the flag, which then has to predict the
     LLM's picks: at least 1.5 tokens per verify step on average, the bar of

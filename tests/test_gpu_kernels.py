@@ -815,9 +815,9 @@ def test_attention_inc_prefill_then_decode(d, layout, fp32):
 
 @pytest.mark.parametrize("d", [32, 64, 128])
 def test_attention_llama3_rope_scaling(d):
-    """llama3 frequency scaling (inc_multihead_self_attention.cu:703-722) in
-    the handle's RoPE table: original_max_position 64 puts the three
-    wavelength branches inside the first 60 positions."""
+    """llama3 frequency scaling (HF's per-pair bands, tests/test_rope_llama3.py)
+    in the handle's RoPE table: original_max_position 64 puts frequency pairs
+    in each of the three wavelength bands."""
     rng = np.random.default_rng(200 + d)
     c = AttnCase(F.ATTN_INC, d=d, theta=500000.0, llama3=(8.0, 1.0, 4.0, 64))
     lens = {0: 33, 1: 57}

@@ -10,7 +10,9 @@ import pytest
 
 import oracle_lib as O
 
-TAGS = ["tiny_d64", "tiny_d128"]
+# the gqa tags: grouped-query attention (4 query heads over 2 K/V heads) and a
+# Llama-3 style multi-query model (G = 4, theta 5e5, llama3 RoPE scaling)
+TAGS = ["tiny_d64", "tiny_d128", "tiny_gqa_d64", "tiny_gqa_d128_llama3"]
 
 
 def test_weight_generator_matches_numpy_twin():
@@ -63,8 +65,8 @@ def test_oracle_fp16_within_half_tolerance(tag):
     assert bad.mean() <= 0.05
 
 
-def test_oracle_batched_decode_matches_per_request():
-    cfg, g = O.load_golden("tiny_d64")
+def test_oracle_batched_decode_matches_per_request(tag="tiny_d64"):
+    cfg, g = O.load_golden(tag)
     m1 = O.Model(cfg, cfg["seed"], fp16=1, max_requests=3, max_seq=64)
     m2 = O.Model(cfg, cfg["seed"], fp16=1, max_requests=3, max_seq=64)
     prompts = [[1, 5, 9, 33], [1, 7], [1, 2, 3, 4, 5, 6]]
@@ -77,6 +79,10 @@ def test_oracle_batched_decode_matches_per_request():
     for r in range(3):
         ls = m2.forward(r, [nxt[r]], pos[r])
         np.testing.assert_array_equal(lb[r], ls[0])
+
+
+def test_oracle_batched_decode_matches_per_request_gqa():
+    test_oracle_batched_decode_matches_per_request("tiny_gqa_d64")
 
 
 # ------------------------------------------------- reference half compute type
@@ -143,11 +149,11 @@ def test_oracle_ref16_within_half_tolerance(tag):
     assert not np.array_equal(logits, O.Model(cfg, cfg["seed"], fp16=1).forward(0, g["prompt"], 0))
 
 
-def test_oracle_forward_multi_equals_per_request_forwards():
+def test_oracle_forward_multi_equals_per_request_forwards(num_kv_heads=4):
     """orc_model_forward_multi (the CPU port of a verify / beam step used by
     bench.py's cpu_baseline) batches the dense layers over several requests'
-    blocks: bit-identical to one orc_model_forward per request."""
-    cfg = dict(num_layers=2, vocab_size=500, num_heads=4, num_kv_heads=4, hidden=128,
+    blocks: bit-identical to one orc_model_forward per request (MHA and GQA)."""
+    cfg = dict(num_layers=2, vocab_size=500, num_heads=4, num_kv_heads=num_kv_heads, hidden=128,
                intermediate=256, rms_eps=1e-6, rope_theta=10000.0)
     a = O.Model(cfg, 3, fp16=1, max_requests=3, max_seq=64)
     b = O.Model(cfg, 3, fp16=1, max_requests=3, max_seq=64)
@@ -160,6 +166,10 @@ def test_oracle_forward_multi_equals_per_request_forwards():
     ref = np.vstack([a.forward(r, blk, len(prompts[r])) for r, blk in enumerate(blocks)])
     got = b.forward_multi([0, 1, 2], [3, 1, 6], [len(p) for p in prompts], np.concatenate(blocks))
     assert np.array_equal(ref.view(np.uint32), got.view(np.uint32))
+
+
+def test_oracle_forward_multi_equals_per_request_forwards_gqa():
+    test_oracle_forward_multi_equals_per_request_forwards(num_kv_heads=2)
 
 
 def test_token_chain_init_scale_and_chain():

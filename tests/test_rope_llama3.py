@@ -1,7 +1,11 @@
 """llama3 RoPE scaling of the oracle's table against a numpy restatement of
-the reference's formula (inc_multihead_self_attention.cu:701-725): f32
-arithmetic, freq = pos * (1.0 / pow(theta, 2i/d)) in the float/double mix,
-and the wavelength taken of the position-scaled freq, as the reference does.
+HF transformers' definition (modeling_rope_utils._compute_llama3_parameters,
+the Llama-3 release's apply_scaling): f32 arithmetic, inv_freq = 1.0 /
+pow(theta, 2i/d), the band chosen per frequency pair from the wavelength
+2*pi / inv_freq, and freq = pos * scaled inv_freq.  (The reference,
+inc_multihead_self_attention.cu:704-722, takes the wavelength of the
+position-scaled freq instead; tests/test_oracle_golden.py's llama3 fixture, made
+by HF, rejects that.)
 """
 import numpy as np
 import pytest
@@ -14,27 +18,24 @@ def ref_table(max_pos, d, theta, llama3=None):
     h = d // 2
     ex = (f32(2) * np.arange(h, dtype=f32) / f32(d)).astype(f32)
     inv = 1.0 / np.power(f32(theta), ex).astype(np.float64)
+    if llama3:
+        factor, lo, hi, orig = (f32(llama3[0]), f32(llama3[1]), f32(llama3[2]), f32(llama3[3]))
+        low_wl, high_wl = f32(orig / lo), f32(orig / hi)
+        pi = f32(3.141592654)
+        for i in range(h):
+            f = f32(inv[i])
+            wl = f32(f32(2) * pi / f)
+            if wl < high_wl:
+                continue
+            if wl > low_wl:
+                f = f32(f / factor)
+            else:
+                sm = f32(f32(f32(orig / wl) - lo) / f32(hi - lo))
+                f = f32(f32(f32(f32(f32(1) - sm) * f) / factor) + f32(sm * f))
+            inv[i] = np.float64(f)
     tab = np.zeros((max_pos, h, 2), f32)
-    pi = f32(3.141592654)
     for p in range(max_pos):
         freq = (p * inv).astype(f32)
-        if llama3:
-            factor, lo, hi, orig = (f32(llama3[0]), f32(llama3[1]), f32(llama3[2]),
-                                    f32(llama3[3]))
-            low_wl, high_wl = f32(orig / lo), f32(orig / hi)
-            with np.errstate(divide="ignore"):
-                wl = (f32(2) * pi / freq).astype(f32)
-            out = freq.copy()
-            for i in range(h):
-                if wl[i] < high_wl:
-                    continue
-                if wl[i] > low_wl:
-                    out[i] = f32(freq[i] / factor)
-                else:
-                    sm = f32(f32(f32(orig / wl[i]) - lo) / f32(hi - lo))
-                    a = f32(f32(f32(f32(1) - sm) * freq[i]) / factor)
-                    out[i] = f32(a + f32(sm * freq[i]))
-            freq = out
         tab[p, :, 0] = np.cos(freq.astype(np.float64)).astype(f32)
         tab[p, :, 1] = np.sin(freq.astype(np.float64)).astype(f32)
     return tab.reshape(max_pos, d)
@@ -56,9 +57,17 @@ def test_llama3_scaling_changes_only_long_wavelengths():
     base = O.rope_table(200, 128, 500000.0)
     l3 = O.rope_table(200, 128, 500000.0, (8.0, 1.0, 4.0, 64))
     assert np.array_equal(base[0], l3[0])            # pos 0: freq 0 either way
-    # high-frequency pairs (wavelength < 16 at pos 100) are untouched
-    assert np.array_equal(base[100, :8], l3[100, :8])
+    # high-frequency pairs (wavelength 2*pi / inv_freq < 16: pairs 0..3) are untouched
+    assert np.array_equal(base[:, :8], l3[:, :8])
     assert not np.array_equal(base[100], l3[100])
+    # the band belongs to the pair, not to the position: the lowest-frequency
+    # pair (wavelength > 64) runs at 1/8 of its frequency at every position
+    h = 64
+    inv = np.float32(1.0) / np.power(np.float32(500000.0), np.float32(2 * (h - 1)) / np.float32(128))
+    for p in (1, 7, 150):
+        want = np.float32(p * np.float64(np.float32(inv / np.float32(8))))
+        assert abs(l3[p, 2 * (h - 1)] - np.cos(np.float64(want))) <= 1e-6
+        assert abs(l3[p, 2 * (h - 1) + 1] - np.sin(np.float64(want))) <= 1e-6
 
 
 def test_llama_config_from_hf_reads_llama3_scaling(tmp_path):

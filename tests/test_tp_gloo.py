@@ -55,6 +55,13 @@ def _tp_forward(rank, world, tag, out_path, port):
         nh = cfg["num_heads"]
         d = H // nh
         Hl, Fl, hl = H // world, F // world, nh // world
+        # grouped-query attention: k/v_proj at num_kv_heads heads, sharded by
+        # K/V heads (rank s: K/V heads [s*kvl, (s+1)*kvl)); local query head hh
+        # attends over local K/V head hh // G, as the unsharded head s*hl + hh
+        # over (s*hl + hh) // G
+        nkv = cfg.get("num_kv_heads", nh)
+        Hkv, kvl, G = nkv * d, nkv // world, nh // nkv
+        Hkvl = kvl * d
         eps = cfg["rms_eps"]
 
         def W(name, rows, cols, kind=0):
@@ -81,15 +88,15 @@ def _tp_forward(rank, world, tag, out_path, port):
             p = f"model.layers.{layer}."
             h = O.rmsnorm(x, O.gen_weight(p + "input_layernorm.weight", seed, 1, H), eps, 0)
             q = O.linear(h, W(p + "self_attn.q_proj.weight", H, H)[s * Hl:(s + 1) * Hl], 0)
-            k = O.linear(h, W(p + "self_attn.k_proj.weight", H, H)[s * Hl:(s + 1) * Hl], 0)
-            v = O.linear(h, W(p + "self_attn.v_proj.weight", H, H)[s * Hl:(s + 1) * Hl], 0)
-            q, k = rope(q.reshape(T, hl, d)), rope(k.reshape(T, hl, d))
-            v = v.reshape(T, hl, d)
+            k = O.linear(h, W(p + "self_attn.k_proj.weight", Hkv, H)[s * Hkvl:(s + 1) * Hkvl], 0)
+            v = O.linear(h, W(p + "self_attn.v_proj.weight", Hkv, H)[s * Hkvl:(s + 1) * Hkvl], 0)
+            q, k = rope(q.reshape(T, hl, d)), rope(k.reshape(T, kvl, d))
+            v = v.reshape(T, kvl, d)
             att = np.zeros((T, hl, d), np.float32)
             for hh in range(hl):
                 for t in range(T):
                     vis = np.arange(T) <= t
-                    att[t, hh] = O.attention_row(q[t, hh], k[:, hh], v[:, hh], vis,
+                    att[t, hh] = O.attention_row(q[t, hh], k[:, hh // G], v[:, hh // G], vis,
                                                  1.0 / np.sqrt(d), 0)
             wo = W(p + "self_attn.o_proj.weight", H, H)[:, s * Hl:(s + 1) * Hl]
             o = allreduce(O.linear(att.reshape(T, Hl), wo, 0))
@@ -147,7 +154,7 @@ def _run_ranks(code_args, world=2, timeout=300):
         assert p.returncode == 0, e.decode()[-3000:]
 
 
-@pytest.mark.parametrize("tag", ["tiny_d64", "tiny_d128"])
+@pytest.mark.parametrize("tag", ["tiny_d64", "tiny_d128", "tiny_gqa_d64"])
 def test_tp2_decomposition_matches_unsharded_golden(tag, tmp_path):
     sys.path.insert(0, HERE)
     import oracle_lib as O
