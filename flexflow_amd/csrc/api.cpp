@@ -53,7 +53,9 @@ extern "C" const char *ffmi_status_str(ffmi_status s) {
 // test hooks;
 // then native grouped-query attention, again by addition only:
 // ffmi_attn_create_gqa, ffmi_attn_cache_bytes, ffmi_attn_set_gqa_route,
-// ffmi_model_create_ex (FFMI_MODEL_NATIVE_GQA), ffmi_model_kv_cache_bytes
+// ffmi_model_create_ex (FFMI_MODEL_NATIVE_GQA), ffmi_model_kv_cache_bytes;
+// then per-token log-probabilities, by addition only: ffmi_token_logprobs,
+// ffmi_token_logprobs_workspace_bytes, ffmi_model_set_logprobs, ffmi_rm_get_logprobs
 extern "C" const char *ffmi_version(void) { return "ffmi 0.4 (gfx950)"; }
 
 // ---------------------------------------------------------------------------
@@ -67,12 +69,14 @@ extern "C" ffmi_status ffmi_batch_create(int max_tokens, int max_requests, ffmi_
   b->max_tokens = max_tokens;
   b->max_requests = max_requests;
   // header + tokens + work (<= tokens) + commits (<= tokens) + masks, and
-  // room behind them for one float per token (a sampling model's draws)
+  // room behind them for one float per token (a sampling model's draws) and
+  // one id per token (the targets of a model with logprobs on)
   b->cap = align16(sizeof(ffmi::BatchHeader)) + align16((size_t)max_tokens * sizeof(ffmi_token_info)) +
            align16((size_t)max_tokens * sizeof(ffmi::WorkDev)) +
            align16((size_t)max_tokens * sizeof(ffmi_commit_info)) +
            align16((size_t)max_requests * FFMI_MAX_TREE * sizeof(uint64_t)) + 64 +
-           align16((size_t)max_tokens * sizeof(float));
+           align16((size_t)max_tokens * sizeof(float)) +
+           align16((size_t)max_tokens * sizeof(int32_t));
   // fine-grained (uncached on the device) and mapped: the model's first
   // kernel reads the step's blob straight from here (launch_rmsnorm's fetch)
   if (hipHostMalloc((void **)&b->host, b->cap, hipHostMallocCoherent | hipHostMallocMapped) !=
@@ -693,6 +697,24 @@ extern "C" ffmi_status ffmi_sample_topp(const void *logits, int T, int V, float 
              FFMI_ERR_INVALID);
   FFMI_HIP(ffmi::launch_sample_topp((const uint16_t *)logits, T, V, temperature, topp, u, ids, probs,
                                     workspace, workspace_bytes, (hipStream_t)stream));
+  return FFMI_OK;
+}
+
+extern "C" size_t ffmi_token_logprobs_workspace_bytes(int T, int V) {
+  return ffmi::token_logprobs_workspace_bytes(T, V);
+}
+
+extern "C" ffmi_status ffmi_token_logprobs(const void *logits, int T, int V, float temperature,
+                                           const int32_t *targets, const int32_t *picks,
+                                           float *logprobs, void *workspace,
+                                           size_t workspace_bytes, ffmi_stream stream) {
+  FFMI_CHECK(logits && logprobs && T >= 0 && V >= 1 && (targets || picks), FFMI_ERR_INVALID);
+  FFMI_CHECK(temperature >= 0.f && temperature <= 3.4028234664e38f, FFMI_ERR_INVALID);  // (NaN, inf)
+  FFMI_CHECK(V <= ffmi::sample_topp_max_v(), FFMI_ERR_UNSUPPORTED);
+  FFMI_CHECK(T == 0 || (workspace && workspace_bytes >= ffmi::token_logprobs_workspace_bytes(T, V)),
+             FFMI_ERR_INVALID);
+  FFMI_HIP(ffmi::launch_token_logprobs((const uint16_t *)logits, T, V, temperature, targets, picks,
+                                       logprobs, workspace, (hipStream_t)stream));
   return FFMI_OK;
 }
 

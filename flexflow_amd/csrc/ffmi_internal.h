@@ -257,6 +257,13 @@ hipError_t launch_sample_topp(const uint16_t *logits, int T, int V, float temper
                               size_t ws_bytes, hipStream_t s);
 size_t sample_topp_workspace_bytes(int T, int V);
 int sample_topp_max_v();  // the longest row (or shard of one) the sampling kernels take
+// per-token log-probabilities (include/ffmi.h ffmi_token_logprobs): the scored
+// id of row t is targets[t] when targets is given and that is >= 0, else picks[t]
+constexpr int kLogprobChunk = 4096;  // logits per (m, s) pair, the same for every T
+size_t token_logprobs_workspace_bytes(int T, int V);
+hipError_t launch_token_logprobs(const uint16_t *logits, int T, int V, float temperature,
+                                 const int32_t *targets, const int32_t *picks, float *logprobs,
+                                 void *ws, hipStream_t s);
 // Vocab-sharded tail (vshard_kernel): phase 0..2 write this rank's exchange
 // record ([P][T][W] floats, W >= max(4, 2k)); phase 3 merges into ids/probs.
 hipError_t launch_vshard(const uint16_t *logits, int T, int Vl, int P, int rank, int k,

@@ -1,5 +1,6 @@
 // sampling.hip -- the fp16 token pick: softmax + argmax / arg-top-k, top-p
-// sampling, and both under a vocab-sharded lm_head.
+// sampling, and both under a vocab-sharded lm_head; and, at the end, the
+// log-probability of a row's scored id (its own rule: the full softmax in fp32).
 //
 // Five kernels implement one rule -- p_i = half(expf(x_i - M) / S) with S =
 // float(double sum), ordered by (p desc, index asc) -- and every decision of
@@ -1154,6 +1155,146 @@ hipError_t launch_vshard_sample(const uint16_t *logits, int Vl, int P, int rank,
     default: return hipErrorInvalidValue;
   }
 #undef FFMI_VS
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// Per-token log-probabilities (include/ffmi.h ffmi_token_logprobs): the log of
+// the full softmax of z (the logits, or the row the top-p pick sees: z =
+// half(x / half(temperature)), temper_row's expression) at one scored id,
+//   lp = (z_s - M) - log(S),  M = max z,  S = sum exp(z - M)  in fp32.
+// Nothing here is ranked or tied, so the hardware exp2 serves for the terms
+// (the bar is 2^-16 + 2^-21 |lp|, ten times the fp32 rule's own error).
+// A row's bits depend on the row alone: it is cut into chunks of kLogprobChunk
+// logits whatever T is; one workgroup reduces one chunk to (m, s = sum exp(z -
+// m)), every thread taking the same 16 elements in the same order and the
+// waves' sums added in wave order; the second launch, one thread per row,
+// takes M = max m_c and adds the s_c exp(m_c - M) in chunk order.  No atomics.
+// T x ceil(V / 4096) workgroups of 256 threads: 64 at T = 8, V = 32000 (a
+// decode step), 256 at V = 128256.
+// ---------------------------------------------------------------------------
+extern "C" __device__ float __ockl_wfred_add_f32(float);
+constexpr int kLpTPB = 256;
+constexpr int kLpVec = 8;                                    // logits per 16-byte load
+constexpr int kLpLoads = kLogprobChunk / (kLpTPB * kLpVec);  // per thread
+static_assert(kLpLoads * kLpTPB * kLpVec == kLogprobChunk, "a chunk is whole loads");
+
+template <bool TEMPER>
+__device__ __forceinline__ float lp_z(uint16_t x, float th) {
+  return TEMPER ? h2f_(f2h_(__fdiv_rn(h2f_(x), th))) : h2f_(x);
+}
+
+// VEC: 16-byte loads (V % 8 == 0 and an aligned base: every group of 8 lies
+// whole inside or outside the row); the element -> thread map and the order of
+// the sums are the same in both forms, so their bits are
+template <bool TEMPER, bool VEC>
+__global__ __launch_bounds__(kLpTPB) void logprob_chunk_kernel(
+    const uint16_t *__restrict__ logits, int V, int nchunk, float temperature,
+    float2 *__restrict__ part) {
+  constexpr int NW = kLpTPB / 64;
+  __shared__ float shm[NW], shs[NW];
+  const int row = blockIdx.x / nchunk, c = blockIdx.x % nchunk;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const uint16_t *x = logits + (size_t)row * V;
+  const float th = TEMPER ? h2f_(f2h_(temperature)) : 0.f;
+  float z[kLpLoads * kLpVec];
+#pragma unroll
+  for (int j = 0; j < kLpLoads; ++j) {
+    // (c * kLogprobChunk < V <= 983040: no overflow)
+    const int i0 = c * kLogprobChunk + (j * kLpTPB + tid) * kLpVec;
+    if (VEC) {
+      uint4 r = make_uint4(0xfc00fc00u, 0xfc00fc00u, 0xfc00fc00u, 0xfc00fc00u);  // -inf
+      if (i0 < V) r = *reinterpret_cast<const uint4 *>(x + i0);
+#pragma unroll
+      for (int e = 0; e < kLpVec; ++e) {
+        const uint32_t w = (&r.x)[e >> 1];
+        const uint16_t hv = (uint16_t)((e & 1) ? w >> 16 : w & 0xffffu);
+        z[j * kLpVec + e] = i0 < V ? lp_z<TEMPER>(hv, th) : -INFINITY;
+      }
+    } else {
+#pragma unroll
+      for (int e = 0; e < kLpVec; ++e)
+        z[j * kLpVec + e] = i0 + e < V ? lp_z<TEMPER>(x[i0 + e], th) : -INFINITY;
+    }
+  }
+  float m = z[0];
+#pragma unroll
+  for (int e = 1; e < kLpLoads * kLpVec; ++e) m = fmaxf(m, z[e]);
+  m = __ockl_wfred_max_f32(m);
+  if (lane == 0) shm[wv] = m;
+  __syncthreads();
+  m = shm[0];
+#pragma unroll
+  for (int q = 1; q < NW; ++q) m = fmaxf(m, shm[q]);
+  // (a chunk of -inf logits only: s = 0, and the combine gives it no weight)
+  const float mm = m == -INFINITY ? 0.f : m;
+  float s = 0.f;
+#pragma unroll
+  for (int e = 0; e < kLpLoads * kLpVec; ++e) s += __expf(z[e] - mm);
+  s = __ockl_wfred_add_f32(s);
+  if (lane == 0) shs[wv] = s;
+  __syncthreads();
+  if (tid == 0) {
+    float t = shs[0];
+#pragma unroll
+    for (int q = 1; q < NW; ++q) t += shs[q];
+    part[blockIdx.x] = make_float2(m, t);
+  }
+}
+
+template <bool TEMPER>
+__global__ __launch_bounds__(64) void logprob_combine_kernel(
+    const uint16_t *__restrict__ logits, int T, int V, int nchunk, float temperature,
+    const int32_t *__restrict__ targets, const int32_t *__restrict__ picks,
+    const float2 *__restrict__ part, float *__restrict__ logprobs) {
+  const int row = blockIdx.x * 64 + threadIdx.x;
+  if (row >= T) return;
+  int id = targets ? targets[row] : -1;
+  if (id < 0 && picks) id = picks[row];
+  if (id < 0 || id >= V) {  // (outside the contract: no logit is read)
+    logprobs[row] = __uint_as_float(0x7fc00000u);
+    return;
+  }
+  const float2 *p = part + (size_t)row * nchunk;
+  float M = p[0].x;
+  for (int c = 1; c < nchunk; ++c) M = fmaxf(M, p[c].x);
+  float S = 0.f;
+  for (int c = 0; c < nchunk; ++c) S += p[c].y * expf(p[c].x - M);
+  const float th = TEMPER ? h2f_(f2h_(temperature)) : 0.f;
+  const float zs = lp_z<TEMPER>(logits[(size_t)row * V + id], th);
+  logprobs[row] = (zs - M) - logf(S);
+}
+
+static int logprob_chunks(int V) { return (V + kLogprobChunk - 1) / kLogprobChunk; }
+size_t token_logprobs_workspace_bytes(int T, int V) {
+  return T <= 0 || V <= 0 ? 0 : (size_t)T * logprob_chunks(V) * sizeof(float2);
+}
+
+hipError_t launch_token_logprobs(const uint16_t *logits, int T, int V, float temperature,
+                                 const int32_t *targets, const int32_t *picks, float *logprobs,
+                                 void *ws, hipStream_t s) {
+  if (T <= 0) return hipSuccess;
+  const int nchunk = logprob_chunks(V);
+  if (V < 1 || V > kSampleMaxV || !ws || !(temperature >= 0.f) ||
+      (size_t)T * nchunk > (size_t)INT32_MAX)
+    return hipErrorInvalidValue;
+  float2 *part = reinterpret_cast<float2 *>(ws);
+  const bool vec = V % kLpVec == 0 && ((uintptr_t)logits & 15) == 0;
+  const dim3 g1((unsigned)(T * nchunk)), g2((unsigned)((T + 63) / 64));
+#define FFMI_LP(TEMPER)                                                                          \
+  do {                                                                                           \
+    if (vec)                                                                                     \
+      hipLaunchKernelGGL((logprob_chunk_kernel<TEMPER, true>), g1, dim3(kLpTPB), 0, s, logits,  \
+                         V, nchunk, temperature, part);                                          \
+    else                                                                                         \
+      hipLaunchKernelGGL((logprob_chunk_kernel<TEMPER, false>), g1, dim3(kLpTPB), 0, s, logits, \
+                         V, nchunk, temperature, part);                                          \
+    hipLaunchKernelGGL((logprob_combine_kernel<TEMPER>), g2, dim3(64), 0, s, logits, T, V,      \
+                       nchunk, temperature, targets, picks, part, logprobs);                     \
+  } while (0)
+  if (temperature > 0.f) FFMI_LP(true);
+  else FFMI_LP(false);
+#undef FFMI_LP
   return hipGetLastError();
 }
 

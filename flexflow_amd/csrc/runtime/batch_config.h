@@ -52,6 +52,10 @@ class BatchConfig {
     int abs_depth_in_request = 0;
     int request_index = 0;
     TokenId token_id = 0;
+    // the id whose log-probability this row's logits are to give (a model
+    // with logprobs on): the request's next token where it is already known
+    // (prompt rows), -1 for the step's own pick.  Not in the reference.
+    TokenId score_id = -1;
   };
   struct BitMask {
     uint64_t mask[MAX_SPEC_TREE_TOKEN_NUM] = {0};
@@ -83,6 +87,9 @@ class TreeVerifyBatchConfig : public BatchConfig {
 struct InferenceResult {
   static constexpr int MAX_NUM_TOKENS = BatchConfig::MAX_NUM_TOKENS;
   BatchConfig::TokenId token_ids[MAX_NUM_TOKENS];
+  // log-probability of each row's scored id (PerTokenInfo::score_id); written
+  // only by a model with logprobs on
+  float logprobs[MAX_NUM_TOKENS];
 };
 
 class BeamSearchBatchConfig : public BatchConfig {

@@ -58,6 +58,11 @@ extern "C" ffmi_status ffmi_model_set_sampling(ffmi_model *m, int do_sample, flo
   return m->set_sampling(do_sample != 0, temperature, topp, seed);
 }
 
+extern "C" ffmi_status ffmi_model_set_logprobs(ffmi_model *m, int enable) {
+  if (!m) return FFMI_ERR_INVALID;
+  return m->set_logprobs(enable != 0);
+}
+
 extern "C" long ffmi_model_debug_tensor(ffmi_model *m, int which, int layer, float *out,
                                         long cap) {
   if (!m || !out || cap <= 0) return -1;
@@ -202,6 +207,15 @@ extern "C" int ffmi_rm_get_output(ffmi_rm *rm, int64_t guid, int *tokens, int ca
   if (!gr) return -1;
   const int n = (int)gr->output_tokens.size();
   for (int i = 0; i < n && i < cap && tokens; ++i) tokens[i] = gr->output_tokens[i];
+  return n;
+}
+
+extern "C" int ffmi_rm_get_logprobs(ffmi_rm *rm, int64_t guid, float *out, int cap) {
+  if (!rm) return -1;
+  const ffmi::GenerationResult *gr = rm->rm.get_generation_result(guid);
+  if (!gr) return -1;
+  const int n = (int)gr->logprobs.size();
+  for (int i = 0; i < n && i < cap && out; ++i) out[i] = gr->logprobs[i];
   return n;
 }
 

@@ -100,6 +100,31 @@ struct HashModel : public ffmi_model {
 
   int next_token(uint64_t h) const { return (int)((h >> 17) % (uint64_t)vocab); }
 
+  // per-token log-probabilities (model.h): a pure function of the row's
+  // context hash and the scored id, in [-1, -2^-24] -- SpecInfer and incremental
+  // decoding then record bit-equal values, and any bookkeeping error changes a
+  // context and therefore a value
+  bool lp_on = false;
+  ffmi_status set_logprobs(bool on) override {
+    if (mode == FFMI_MODEL_BEAM) return ffmi_model::set_logprobs(on);  // (refuses)
+    lp_on = on;
+    return FFMI_OK;
+  }
+  bool logprobs_on() const override { return lp_on; }
+  static float logprob_of(uint64_t h, int id) {
+    const uint64_t x = mix64(h ^ (((uint64_t)(int64_t)id + 1) * 0x9E3779B97F4A7C15ull));
+    return -(float)((x >> 40) + 1) * (1.0f / 16777216.0f);
+  }
+  template <class BC>
+  void fill_results(const BC &bc, const std::vector<uint64_t> &hs, InferenceResult *ir) const {
+    for (size_t t = 0; t < hs.size(); ++t) {
+      ir->token_ids[t] = next_token(hs[t]);
+      if (!lp_on) continue;
+      const int sid = bc.tokensInfo[t].score_id;
+      ir->logprobs[t] = logprob_of(hs[t], sid >= 0 ? sid : ir->token_ids[t]);
+    }
+  }
+
   ffmi_status run_inc(const BatchConfig &bc, InferenceResult *ir) override {
     if (cap >= 0 && bc.num_tokens > cap) return FFMI_ERR_INVALID;
     // (as the GPU model: ids outside the vocabulary are rejected, so a
@@ -111,7 +136,7 @@ struct HashModel : public ffmi_model {
     pack_inc(bc, max_requests, slots, &ps);
     std::vector<uint64_t> hs;
     contexts(ps, &hs);
-    for (size_t t = 0; t < hs.size(); ++t) ir->token_ids[t] = next_token(hs[t]);
+    fill_results(bc, hs, ir);
     return FFMI_OK;
   }
   ffmi_status run_tree(const TreeVerifyBatchConfig &bc, InferenceResult *ir) override {
@@ -125,7 +150,7 @@ struct HashModel : public ffmi_model {
     pack_tree(bc, max_requests, slots, &ps);
     std::vector<uint64_t> hs;
     contexts(ps, &hs);
-    for (size_t t = 0; t < hs.size(); ++t) ir->token_ids[t] = next_token(hs[t]);
+    fill_results(bc, hs, ir);
     return FFMI_OK;
   }
   ffmi_status run_beam(const BeamSearchBatchConfig &bc, BeamInferenceResult *ir) override {

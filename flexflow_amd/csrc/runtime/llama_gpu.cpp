@@ -125,6 +125,62 @@ struct LlamaGPU : public ffmi_model {
     *bytes += n;
     return FFMI_OK;
   }
+  // per-token log-probabilities (ffmi_model_set_logprobs): ffmi_token_logprobs
+  // behind the pick, in the same stream and captured graph.  The rows' targets
+  // (BatchConfig::PerTokenInfo::score_id) ride the blob behind the records and
+  // the draws, as step_u does, so a replayed graph reads fresh ones; the
+  // results go to pinned lp_h.  The picks are read where the device has them:
+  // the greedy tail's argmax leaves a second copy of its ids in lp_picks
+  // (launch_argmax's ids2); the sampling kernel has one ids output, the pinned
+  // results, so under do_sample the combine launch reads each row's pick from
+  // there (4 bytes per row over PCIe, once).
+  bool logprobs = false;
+  float *lp_h = nullptr;        // [Tm], pinned
+  int32_t *lp_picks = nullptr;  // [Tm]
+  char *lp_ws = nullptr;
+  size_t lp_ws_bytes = 0;
+  std::vector<int32_t> step_targets;
+  size_t step_targets_off = 0;
+  bool logprobs_on() const override { return logprobs; }
+  ffmi_status set_logprobs(bool on) override {
+    const char *why = mode == FFMI_MODEL_BEAM
+                          ? "logprobs: a BEAM model's picks are proposals, not tokens"
+                          : Vl != c.vocab_size ? "logprobs: vocab-sharded lm_head" : nullptr;
+    if (why) {
+      ffmi_set_last_error(why, __FILE__, __LINE__);
+      return FFMI_ERR_UNSUPPORTED;
+    }
+    const size_t Tm = (size_t)((o.max_tokens + 15) & ~15);
+    if (on && !lp_ws) {
+      FFMI_CHECK(Vl <= ffmi::sample_topp_max_v(), FFMI_ERR_UNSUPPORTED);
+      if (!lp_h)
+        FFMI_HIP(hipHostMalloc((void **)&lp_h, Tm * sizeof(float),
+                               hipHostMallocCoherent | hipHostMallocMapped));
+      ffmi_status st = lp_picks ? FFMI_OK : alloc(&lp_picks, Tm);
+      if (st != FFMI_OK) return st;
+      lp_ws_bytes = ffmi::token_logprobs_workspace_bytes((int)Tm, Vl);
+      if ((st = alloc(&lp_ws, lp_ws_bytes)) != FFMI_OK) return st;
+    }
+    // (the captured graphs hold the step with or without the launches)
+    FFMI_HIP(hipStreamSynchronize(stream));
+    clear_graphs();
+    logprobs = on;
+    return FFMI_OK;
+  }
+  // the step's targets, from the batch the scheduler built, appended to the
+  // staged blob (forward_launch, behind the draws)
+  void take_step_targets(const BatchConfig &bc) {
+    step_targets.resize(bc.num_tokens);
+    for (int t = 0; t < bc.num_tokens; ++t) step_targets[t] = bc.tokensInfo[t].score_id;
+  }
+  ffmi_status stage_step_targets(int T, size_t *bytes) {
+    step_targets_off = *bytes;
+    const size_t n = ((size_t)T * sizeof(int32_t) + 15) & ~(size_t)15;
+    FFMI_CHECK((int)step_targets.size() == T && *bytes + n <= batch->cap, FFMI_ERR_INVALID);
+    memcpy(batch->host + *bytes, step_targets.data(), (size_t)T * sizeof(int32_t));
+    *bytes += n;
+    return FFMI_OK;
+  }
   // vocab-sharded lm_head at TP > 1 (model.cc:3392-3419): this rank's Vl rows
   // and the [P][Tm][kXW] exchange records of the sharded softmax / top-k
   int Vl = 0;
@@ -200,7 +256,7 @@ struct LlamaGPU : public ffmi_model {
 
   // ---- per-op profiling (HIP events on `stream`) ----
   enum Cat { GEMM_QKV, GEMM_O, GEMM_GATE_UP, GEMM_DOWN, GEMM_LM_HEAD, ATTENTION, NORM,
-             ALLREDUCE, SAMPLING, EMBED, NCAT };
+             ALLREDUCE, SAMPLING, EMBED, LOGPROBS, NCAT };
   struct ProfRec {
     int cat;
     hipEvent_t a, b;
@@ -275,7 +331,8 @@ struct LlamaGPU : public ffmi_model {
   int op_stats(ffmi_op_stat *out, int cap) override {
     static const char *names[NCAT] = {"gemm_qkv", "gemm_o_proj", "gemm_gate_up_silu",
                                       "gemm_down", "gemm_lm_head", "attention", "rmsnorm",
-                                      "rowpar_gemm_allreduce", "softmax_argmax", "embedding"};
+                                      "rowpar_gemm_allreduce", "softmax_argmax", "embedding",
+                                      "token_logprobs"};
     int n = 0;
     for (int i = 0; i < NCAT; ++i) {
       if (opstat[i].launches == 0) continue;
@@ -506,6 +563,7 @@ struct LlamaGPU : public ffmi_model {
     if (comm_stream) (void)hipStreamDestroy(comm_stream);
     for (void *p : allocs) (void)hipFree(p);
     if (ids_h) (void)hipHostFree(ids_h);
+    if (lp_h) (void)hipHostFree(lp_h);
     for (int i = 1; i < kChain; ++i) ffmi_batch_destroy(chain_batch[i]);
     ffmi_batch_destroy(batch);
     if (stream) (void)hipStreamDestroy(stream);
@@ -1011,6 +1069,7 @@ struct LlamaGPU : public ffmi_model {
     if (st != FFMI_OK) return st;
     if (T == 0) return FFMI_OK;
     if (sampling && (st = stage_step_u(T, &bytes)) != FFMI_OK) return st;
+    if (logprobs && (st = stage_step_targets(T, &bytes)) != FFMI_OK) return st;
     probs_h = reinterpret_cast<float *>(ids_h + cur_slot * slot_ints() + (size_t)T * k);
     // graphed: small steps, and tree-verify steps of one work item per
     // request (a fixed shape while the batch is full: T = 168 for 8 requests
@@ -1348,6 +1407,11 @@ struct LlamaGPU : public ffmi_model {
     TRY(enqueue_sampling(k, T));
     prof_end(pr, SAMPLING, (double)T * V * 2, 0);
     mkt();
+    if (logprobs) {
+      pr = prof_begin(ptail);
+      TRY(enqueue_logprobs(k, T));
+      prof_end(pr, LOGPROBS, (double)T * V * 2, 0);
+    }
 #undef TRY
     return FFMI_OK;
   }
@@ -1389,7 +1453,7 @@ struct LlamaGPU : public ffmi_model {
       FFMI_HIP(ffmi::launch_argmax(logits, T, V, k, ids_o, probs_o, stream, topk_ws, topk_ws_bytes,
                                    mode == FFMI_MODEL_BEAM
                                        ? ids_dev + (size_t)cur_slot * (slot_ints() / 2)
-                                       : nullptr));
+                                       : logprobs ? lp_picks : nullptr));
     }
     if (result_copy)
       FFMI_HIP(hipMemcpyAsync(ids_h + cur_slot * slot_ints(), ids_d, (size_t)T * k * 8,
@@ -1398,25 +1462,43 @@ struct LlamaGPU : public ffmi_model {
     return FFMI_OK;
   }
 
+  // the log-probability of every row's scored id, behind the pick
+  // (set_logprobs: INC / TREE, Vl == V, k = 1; targets behind the blob's
+  // records and draws.  The picks: the argmax's device copy, or the pick's ids
+  // output itself -- pinned under do_sample, ids_d with a result copy)
+  ffmi_status enqueue_logprobs(int k, int T) {
+    FFMI_CHECK(k == 1 && lp_ws, FFMI_ERR_INVALID);
+    const int32_t *picks = result_copy ? ids_d
+                           : sampling  ? ids_h + cur_slot * slot_ints()
+                                       : lp_picks;
+    return ffmi_token_logprobs(logits, T, c.vocab_size, sampling ? temperature : 0.f,
+                               reinterpret_cast<const int32_t *>(batch->dev + step_targets_off),
+                               picks, lp_h, lp_ws, lp_ws_bytes, (ffmi_stream)stream);
+  }
+
   ffmi_status run_inc(const BatchConfig &bc, InferenceResult *ir) override {
     if (mode != FFMI_MODEL_INC) return FFMI_ERR_INVALID;
     FFMI_CHECK(bc.num_tokens <= o.max_tokens, FFMI_ERR_INVALID);
     pack_inc(bc, o.max_requests, slots, &ps);
     if (sampling) draw_step_u(bc);
+    if (logprobs) take_step_targets(bc);
     cur_slot = 0;
     ffmi_status st = forward(1);
     if (st != FFMI_OK) return st;
     memcpy(ir->token_ids, ids_h, bc.num_tokens * sizeof(int32_t));
+    if (logprobs) memcpy(ir->logprobs, lp_h, bc.num_tokens * sizeof(float));
     return FFMI_OK;
   }
   ffmi_status run_tree(const TreeVerifyBatchConfig &bc, InferenceResult *ir) override {
     if (mode != FFMI_MODEL_TREE) return FFMI_ERR_INVALID;
     FFMI_CHECK(bc.num_tokens <= o.max_tokens, FFMI_ERR_INVALID);
     pack_tree(bc, o.max_requests, slots, &ps);
+    if (logprobs) take_step_targets(bc);
     cur_slot = 0;
     ffmi_status st = forward(1);
     if (st != FFMI_OK) return st;
     memcpy(ir->token_ids, ids_h, bc.num_tokens * sizeof(int32_t));
+    if (logprobs) memcpy(ir->logprobs, lp_h, bc.num_tokens * sizeof(float));
     return FFMI_OK;
   }
   ffmi_status run_beam(const BeamSearchBatchConfig &bc, BeamInferenceResult *ir) override {

@@ -122,6 +122,17 @@ struct ffmi_model {
                         __LINE__);
     return FFMI_ERR_UNSUPPORTED;
   }
+  // per-token log-probabilities (ffmi_model_set_logprobs): when on, every
+  // step also fills InferenceResult::logprobs, row t scoring
+  // tokensInfo[t].score_id (-1: the step's own pick).  Only fp16 INC / TREE
+  // models with an unsharded vocabulary have it
+  virtual ffmi_status set_logprobs(bool on) {
+    (void)on;
+    ffmi_set_last_error("logprobs: only an fp16 INC or TREE model with an unsharded vocabulary "
+                        "returns log-probabilities", __FILE__, __LINE__);
+    return FFMI_ERR_UNSUPPORTED;
+  }
+  virtual bool logprobs_on() const { return false; }
   virtual long debug_tensor(int which, int layer, float *out, long cap) {
     (void)which;
     (void)layer;

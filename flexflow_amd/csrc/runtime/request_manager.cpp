@@ -143,6 +143,10 @@ void RequestManager::complete_request(Request &request, bool spec) {
   request.status = Request::COMPLETED;
   GenerationResult &gr = request_generation_results[request.guid];
   gr.output_tokens = request.tokens;
+  // one value per output token: what lay beyond the tokens (a dropped EOS,
+  // the max_length cut) goes with them
+  if (record_logprobs) request.logprobs.resize(request.tokens.size(), 0.f);
+  gr.logprobs = request.logprobs;
   ProfileInfo &pi = profiling_requests[request.guid];
   pi.finish_time = now_us();
   num_processed_requests++;
@@ -203,6 +207,10 @@ BatchConfig RequestManager::prepare_next_batch(const BatchConfig &old_bc,
   for (int i = 0; i < old_bc.num_tokens; i++) {
     const RequestGuid guid = old_bc.requestsInfo[old_bc.tokensInfo[i].request_index].request_guid;
     Request &request = all_requests[guid];
+    // the value of the token behind this row: a prompt token the row scored
+    // explicitly, or the pick appended below (score_id -1)
+    if (record_logprobs)
+      set_logprob(request, old_bc.tokensInfo[i].abs_depth_in_request + 1, result.logprobs[i]);
     if (old_bc.tokensInfo[i].abs_depth_in_request + 1 < (int)request.tokens.size()) continue;
     assert(old_bc.tokensInfo[i].abs_depth_in_request + 1 == (int)request.tokens.size());
     ProfileInfo &pi = profiling_requests[guid];
@@ -257,6 +265,7 @@ BatchConfig RequestManager::prepare_next_batch(const BatchConfig &old_bc,
       new_bc.tokensInfo[new_bc.num_tokens].request_index = i;
       new_bc.tokensInfo[new_bc.num_tokens].abs_depth_in_request = depth;
       new_bc.tokensInfo[new_bc.num_tokens].token_id = request.tokens[depth];
+      new_bc.tokensInfo[new_bc.num_tokens].score_id = score_id_of(request, depth);
       new_bc.num_tokens++;
     }
     profiling_requests[R.request_guid].llm_decoding_steps++;
@@ -286,6 +295,7 @@ BatchConfig RequestManager::prepare_next_batch(const BatchConfig &old_bc,
       new_bc.tokensInfo[new_bc.num_tokens].request_index = i;
       new_bc.tokensInfo[new_bc.num_tokens].abs_depth_in_request = j;
       new_bc.tokensInfo[new_bc.num_tokens].token_id = new_request.tokens[j];
+      new_bc.tokensInfo[new_bc.num_tokens].score_id = score_id_of(new_request, j);
       new_bc.num_tokens++;
     }
     if (new_bc.num_tokens == max_tokens_per_batch) break;
@@ -314,6 +324,9 @@ BeamSearchBatchConfig RequestManager::prepare_next_batch_init(
            old_bc.tokensInfo[result_index].request_index == i) {
       const int abs_depth = old_bc.tokensInfo[result_index].abs_depth_in_request;
       const int token_id = result.token_ids[result_index];
+      // a row that scored a known token (prompt rows): its value, once
+      if (record_logprobs && old_bc.tokensInfo[result_index].score_id >= 0)
+        set_logprob(request, abs_depth + 1, result.logprobs[result_index]);
       if (request.status == Request::PENDING) {
         committed_tokens[guid].emplace_back(abs_depth, result_index);
       } else if (abs_depth >= root_abs_depth) {
@@ -327,6 +340,15 @@ BeamSearchBatchConfig RequestManager::prepare_next_batch_init(
           traverse_verify_tree(guid, dfs_tree_inputs.at(guid), tree_outputs);
       stats.tokens_committed += (long)verified_tokens.size();
       stats.request_verifies++;
+      // each verified token is the pick of the row its accepted node occupied:
+      // the result index the walk left in the commit list, entry for entry
+      // (values past a max_length cut leave with complete_request)
+      if (record_logprobs) {
+        const auto &ct = committed_tokens.at(guid);
+        assert(ct.size() == verified_tokens.size());
+        for (size_t j = 0; j < verified_tokens.size(); j++)
+          set_logprob(request, verified_tokens[j].second, result.logprobs[ct[j].second]);
+      }
       // The reference keeps no SpecInfer ttft (its output record has none,
       // :1303-1311); recorded here for the Python results only.
       ProfileInfo &pi = profiling_requests[guid];
@@ -720,6 +742,8 @@ TreeVerifyBatchConfig RequestManager::prepare_next_batch_verify(
           new_bc.tokensInfo[new_bc.num_tokens].request_index = i;
           new_bc.tokensInfo[new_bc.num_tokens].token_id = request.tokens[request.llm_cache_size + j];
           new_bc.tokensInfo[new_bc.num_tokens].abs_depth_in_request = request.llm_cache_size + j;
+          new_bc.tokensInfo[new_bc.num_tokens].score_id =
+              score_id_of(request, request.llm_cache_size + j);
           new_bc.num_tokens++;
         }
         assert(new_bc.num_tokens <= limit);
@@ -1048,6 +1072,7 @@ ffmi_status RequestManager::serve_incr_decoding(ffmi_model *llm) {
   if (!llm) return FFMI_ERR_INVALID;
   apply_limits();
   stats = Stats();
+  record_logprobs = llm->logprobs_on();
   const double t0 = now_us();
   BatchConfig *bc = new BatchConfig();
   InferenceResult *ir = new InferenceResult();
@@ -1403,6 +1428,7 @@ ffmi_status RequestManager::serve_spec_infer(ffmi_model *llm) {
     if (!ssm_models[s]->can_chain_beam()) chain = false;
   apply_limits();
   stats = Stats();
+  record_logprobs = llm->logprobs_on();
   const double t0 = now_us();
   TreeVerifyBatchConfig *tree_bc = new TreeVerifyBatchConfig();
   InferenceResult *tree_ir = new InferenceResult();

@@ -31,6 +31,9 @@ struct Request {
   int llm_cache_size = 0;
   Status status = PENDING;
   std::vector<BatchConfig::TokenId> tokens;
+  // log-probability of tokens[i] given tokens[0 .. i), by position (entry 0:
+  // 0.0); kept only while a serve call records them (an LLM with logprobs on)
+  std::vector<float> logprobs;
   struct BeamTree {
     struct Layer {
       BatchConfig::TokenId tokens[BeamSearchBatchConfig::MAX_SPECULATIVE_TREE_BRANCHES];
@@ -46,6 +49,7 @@ struct Request {
 struct GenerationResult {
   BatchConfig::RequestGuid guid = 0;
   std::vector<BatchConfig::TokenId> input_tokens, output_tokens;
+  std::vector<float> logprobs;  // one per output token, or empty (not recorded)
 };
 
 class RequestManager {
@@ -189,6 +193,19 @@ class RequestManager {
   void complete_request(Request &request, bool spec = false);
   void write_output_record(const Request &request, bool spec) const;
   void apply_limits() const;
+  // per-token log-probabilities (set per serve call from the LLM): the id a
+  // batch row at `depth` scores -- the request's next token where it already
+  // exists, else -1 (the step's own pick) -- and the value of the token at
+  // position pos
+  bool record_logprobs = false;
+  int score_id_of(const Request &request, int depth) const {
+    return record_logprobs && depth + 1 < (int)request.tokens.size() ? request.tokens[depth + 1]
+                                                                     : -1;
+  }
+  static void set_logprob(Request &request, int pos, float lp) {
+    if ((int)request.logprobs.size() <= pos) request.logprobs.resize((size_t)pos + 1, 0.f);
+    request.logprobs[pos] = lp;
+  }
 
   int max_requests_per_batch = 8;
   int max_tokens_per_batch = 128;

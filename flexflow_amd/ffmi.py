@@ -189,6 +189,9 @@ SIGNATURES = {
     "ffmi_sample_topp": (c_int, [c_void_p, c_int, c_int, c_float, c_float, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_size_t, c_void_p]),
     "ffmi_sampling_counter": (ctypes.c_uint32, [c_uint64, c_int64, c_int]),
+    "ffmi_token_logprobs_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "ffmi_token_logprobs": (c_int, [c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_size_t, c_void_p]),
     "ffmi_fill_weight": (c_int, [c_void_p, c_size_t, ctypes.c_char_p, c_uint64, c_int, c_void_p]),
     "ffmi_model_create_ex": (c_int, [ctypes.POINTER(LlamaConfig), ctypes.POINTER(ModelOpts),
                                      ctypes.c_uint, ctypes.POINTER(c_void_p)]),
@@ -200,6 +203,7 @@ SIGNATURES = {
     "ffmi_model_op_stats": (c_int, [c_void_p, ctypes.POINTER(OpStat), c_int]),
     "ffmi_model_set_debug": (c_int, [c_void_p, c_int]),
     "ffmi_model_set_sampling": (c_int, [c_void_p, c_int, c_float, c_float, c_uint64]),
+    "ffmi_model_set_logprobs": (c_int, [c_void_p, c_int]),
     "ffmi_model_debug_tensor": (ctypes.c_long, [c_void_p, c_int, c_int, c_void_p, ctypes.c_long]),
     "ffmi_model_debug_width": (ctypes.c_long, [c_void_p, c_int]),
     "ffmi_model_debug_fault": (c_int, [c_void_p, c_int, c_int, c_int]),
@@ -219,6 +223,7 @@ SIGNATURES = {
     "ffmi_rm_serve_incr_decoding": (c_int, [c_void_p, c_void_p]),
     "ffmi_rm_serve_spec_infer": (c_int, [c_void_p, c_void_p]),
     "ffmi_rm_get_output": (c_int, [c_void_p, c_int64, ctypes.POINTER(c_int), c_int]),
+    "ffmi_rm_get_logprobs": (c_int, [c_void_p, c_int64, ctypes.POINTER(ctypes.c_float), c_int]),
     "ffmi_rm_get_profile": (c_int, [c_void_p, c_int64, ctypes.POINTER(Profile)]),
     "ffmi_rm_get_stats": (c_int, [c_void_p, ctypes.POINTER(ServeStats)]),
     "ffmi_status_str": (ctypes.c_char_p, [c_int]),

@@ -36,7 +36,7 @@ class Model:
                  tp_size=1, comm=None, weights_folder: Optional[str] = None,
                  weight_init: Union[int, str] = 0, full_precision: bool = False,
                  generation_config: Optional[GenerationConfig] = None, sampling_seed: int = 0,
-                 native_gqa: bool = False):
+                 native_gqa: bool = False, logprobs: bool = False):
         """weights_folder: a checkpoint in the reference's per-tensor format
         (see checkpoint.convert_hf_model); None: seeded synthetic weights,
         `weight_init` "uniform" (0, the bench's), "depth_scaled" (1) or
@@ -45,7 +45,8 @@ class Model:
         runtime/llama_f32.cpp); default the fp16 model.  generation_config:
         see set_sampling (None: greedy decoding).  native_gqa: K/V projections
         and the KV cache at num_kv_heads instead of replicated to every query
-        head (FFMI_MODEL_NATIVE_GQA; fp16, num_kv_heads % tp_size == 0)."""
+        head (FFMI_MODEL_NATIVE_GQA; fp16, num_kv_heads % tp_size == 0).
+        logprobs: see set_logprobs."""
         L = F.lib()
         self.config = dict(config)
         self.mode = mode
@@ -61,6 +62,8 @@ class Model:
         self.handle = h
         if generation_config is not None:
             self.set_sampling(generation_config, sampling_seed)
+        if logprobs:
+            self.set_logprobs(True)
 
     def set_sampling(self, generation_config: Optional[GenerationConfig], seed: int = 0):
         """do_sample: every token of this incremental-decoding model is drawn
@@ -78,6 +81,17 @@ class Model:
         F.check(F.lib().ffmi_model_set_sampling(self.handle, int(bool(gc.do_sample)),
                                                 float(gc.temperature), float(gc.topp),
                                                 seed & (2**64 - 1)), "set_sampling")
+
+    def set_logprobs(self, enable: bool = True):
+        """Per-token log-probabilities: requests served by this LLM ("inc" or
+        "tree") come back with GenerationResult.logprobs, the log of the full
+        softmax (at the temperature under do_sample, before any top-p cut) of
+        every output token given the tokens before it, prompt tokens included
+        (include/ffmi.h ffmi_token_logprobs).  Off by default, and then a step
+        is unchanged.  FFMIError (unsupported) on a "beam" model, a
+        full_precision model and a vocab-sharded lm_head
+        (ffmi_model_set_logprobs)."""
+        F.check(F.lib().ffmi_model_set_logprobs(self.handle, int(bool(enable))), "set_logprobs")
 
     def set_profiling(self, level: int):
         F.check(F.lib().ffmi_model_set_profiling(self.handle, level), "set_profiling")
@@ -227,6 +241,10 @@ class GenerationResult:
     latency_us: float = 0.0
     ttft_us: float = 0.0
     output_text: str = ""  # tokenizer.decode(output_tokens) when one is registered
+    # log P(output_tokens[i] | output_tokens[:i]) when the LLM had logprobs on
+    # (Model.set_logprobs): entry 0, which has no predecessor, is None; None
+    # altogether when nothing was recorded
+    logprobs: Optional[List[Optional[float]]] = None
 
 
 class RequestManager:
@@ -397,9 +415,15 @@ class RequestManager:
             if (getattr(self.tokenizer, "old_llama_tokenizer", False) and
                     self._add_special.get(guid, True) and out and out[0] == self._bos):
                 text = "<s> " + text
+        lps = None
+        m = L.ffmi_rm_get_logprobs(self.handle, guid, None, 0)
+        if m > 0:
+            fbuf = (ctypes.c_float * m)()
+            L.ffmi_rm_get_logprobs(self.handle, guid, fbuf, m)
+            lps = [None] + [float(v) for v in fbuf[1:m]]
         return GenerationResult(guid, out[:p.input_len], out, p.llm_decoding_steps,
                                 p.ssm_decoding_steps, p.finish_us - p.start_us,
-                                p.first_token_us - p.registration_us, text)
+                                p.first_token_us - p.registration_us, text, lps)
 
     def stats(self) -> F.ServeStats:
         s = F.ServeStats()

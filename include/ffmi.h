@@ -410,6 +410,35 @@ ffmi_status ffmi_sample_topp(const void *logits, int T, int V, float temperature
  * position only -- not on the batch around it, the prefill chunking or graph
  * replay. */
 uint32_t ffmi_sampling_counter(uint64_t seed, int64_t guid, int pos);
+/* Per-token log-probabilities: the log of the full softmax of a row at one
+ * scored id s (no top-p cut: under sampling it is the distribution at the
+ * temperature, not the truncated one).  With R16 as above,
+ *   z_i = x_i                                       (temperature == 0)
+ *   z_i = R16(float(x_i) / float(R16(temperature))) (temperature > 0: the row
+ *                                                    ffmi_sample_topp sees)
+ *   M   = max_i z_i
+ *   S   = sum_i exp(float(z_i) - M)                 fp32
+ *   lp  = (float(z_s) - M) - log(S)                 fp32, in this order
+ * ((z_s - M) first: M + log S first cancels everything at large logits).
+ * Row t scores targets[t] when it is >= 0 and picks[t] otherwise; targets ==
+ * NULL scores every row's pick.  picks is the ids output of the pick kernel
+ * earlier on the same stream (ids in [0, V)); an id outside [0, V) writes a
+ * quiet NaN for its row and reads no logit.  lp <= 0, and lp == 0 for V == 1.
+ * A row's bits depend on the row, the temperature and the id only -- not on T,
+ * the row's index or the launch shape: the row is cut into chunks of 4096
+ * logits, every chunk reduced the same way by one workgroup to (m, s), and the
+ * chunks' pairs combined in chunk order (no float atomics).  Two launches,
+ * graph-capturable; logprobs (and picks) may be pinned host memory.
+ * `workspace` holds ffmi_token_logprobs_workspace_bytes(T, V) bytes of device
+ * memory (any contents), one per stream in flight.  Decided before any HIP
+ * call -- FFMI_ERR_INVALID: T < 0, V < 1, a null logits / logprobs, a null
+ * picks while targets is null, a temperature that is negative or not finite,
+ * a missing or short workspace; FFMI_ERR_UNSUPPORTED: V > 983040.  T == 0:
+ * FFMI_OK, nothing launched. */
+size_t ffmi_token_logprobs_workspace_bytes(int T, int V);
+ffmi_status ffmi_token_logprobs(const void *logits, int T, int V, float temperature,
+                                const int32_t *targets, const int32_t *picks, float *logprobs,
+                                void *workspace, size_t workspace_bytes, ffmi_stream stream);
 /* DT_FLOAT twins (--use-full-precision, kernels/f32.hip): RMSNorm /
  * ResidualRMSNorm (sum of squares in fp64, rounded once; fp32 residual add),
  * SigmoidSiluMulti, softmax + arg-top-k on fp32 probabilities (k <= 4, lowest
@@ -569,6 +598,16 @@ ffmi_status ffmi_model_set_debug(ffmi_model *m, int enable);
  * greedy token tree) and a full_precision model. */
 ffmi_status ffmi_model_set_sampling(ffmi_model *m, int do_sample, float temperature, float topp,
                                     uint64_t seed);
+/* enable != 0: every step of an fp16 INC or TREE model also runs
+ * ffmi_token_logprobs behind its pick, in the same stream and captured graph
+ * (temperature: the model's when it samples, 0 otherwise), and its results
+ * carry one log-probability per row; a serve call with such an LLM records
+ * them per request (ffmi_rm_get_logprobs).  Off (the default): no launch and
+ * no byte is added to a step.  Toggling synchronises the stream and drops the
+ * captured graphs.  FFMI_ERR_UNSUPPORTED ("logprobs" in ffmi_last_error): a
+ * BEAM model (an SSM's picks are proposals), a full_precision model, a
+ * vocab-sharded lm_head (tensor parallelism over the vocabulary). */
+ffmi_status ffmi_model_set_logprobs(ffmi_model *m, int enable);
 long ffmi_model_debug_tensor(ffmi_model *m, int which, int layer, float *out, long cap);
 long ffmi_model_debug_width(ffmi_model *m, int which);
 /* Negative-control fault injection (tests only; never set in serving): the
@@ -673,6 +712,13 @@ ffmi_status ffmi_rm_serve_incr_decoding(ffmi_rm *rm, ffmi_model *llm);
 ffmi_status ffmi_rm_serve_spec_infer(ffmi_rm *rm, ffmi_model *llm);
 /* GenerationResult.output_tokens; returns count (or needed size) */
 int ffmi_rm_get_output(ffmi_rm *rm, int64_t guid, int *tokens, int cap);
+/* The log-probability of every output token given the tokens before it, when
+ * the request was served by an LLM with ffmi_model_set_logprobs on: as many
+ * entries as output tokens, prompt included (a prompt token's value is the
+ * model's for that token, a generated token's the value of its pick); entry 0,
+ * which has no predecessor, is 0.0.  Returns the count (or needed size), 0
+ * when nothing was recorded, -1 for an unknown guid. */
+int ffmi_rm_get_logprobs(ffmi_rm *rm, int64_t guid, float *out, int cap);
 typedef struct {
   int llm_decoding_steps, ssm_decoding_steps;
   double start_us, finish_us, registration_us, first_token_us;
@@ -827,7 +873,9 @@ const char *ffmi_last_error(void);
  * consumers and the gather norm: ffmi_debug_partials_reduce,
  * ffmi_debug_rmsnorm_partials, ffmi_debug_attn_partials,
  * ffmi_debug_allreduce_partials, ffmi_debug_rmsnorm_gather; and of the
- * output projection folded into the fused attention: ffmi_debug_attn_oproj */
+ * output projection folded into the fused attention: ffmi_debug_attn_oproj;
+ * and per-token log-probabilities: ffmi_token_logprobs(_workspace_bytes),
+ * ffmi_model_set_logprobs, ffmi_rm_get_logprobs */
 const char *ffmi_version(void);
 
 #ifdef __cplusplus
