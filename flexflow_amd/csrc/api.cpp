@@ -349,8 +349,10 @@ static ffmi_status attn_create(const ffmi_attn_cfg *cfg, int kv_heads, ffmi_attn
     ffmi_set_last_error("attention cache alloc", __FILE__, __LINE__);
     return FFMI_ERR_OOM;
   }
-  // zero the caches: masked keys are multiplied by exactly-zero weights, so
-  // never-written slots must hold finite values
+  // zero the caches: a masked key below a work item's kv_len is multiplied by
+  // an exactly-zero weight, so a slot there must hold finite values (its
+  // request has written it; slots at and past kv_len, where a recycled request
+  // slot keeps its last occupant's rows, enter no product: attention.hip)
   FFMI_HIP(hipMemset(h->kc, 0, kv * es));
   FFMI_HIP(hipMemset(h->vc, 0, kv * es));
   if (h->stage)

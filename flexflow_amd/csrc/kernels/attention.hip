@@ -514,6 +514,19 @@ __global__ __launch_bounds__(64 * NW, 1) void attention_kernel(
       va[t] = h8{v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
     }
   };
+  // the V^T columns of the chunk's slots >= kv_len as zeros (a lane holds the
+  // slots base + 4 g + r and base + 16 + 4 g + r, r < 4, of every d-tile)
+  auto zero_past_kv_len = [&](int base, h8 (&va)[DT]) {
+    typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+    const int n0 = w.kv_len - (base + 4 * g), n1 = n0 - 16;  // slots of each half below kv_len
+    auto pair = [](int n, int k) {  // mask of the half's fp16 pair k
+      return n >= 2 * k + 2 ? 0xffffffffu : n == 2 * k + 1 ? 0xffffu : 0u;
+    };
+    const u4 m = {pair(n0, 0), pair(n0, 1), pair(n1, 0), pair(n1, 1)};
+#pragma unroll
+    for (int t = 0; t < DT; ++t)
+      va[t] = __builtin_bit_cast(h8, __builtin_bit_cast(u4, va[t]) & m);
+  };
   // FUSED: every slot this step writes for the request (its stores and TREE
   // commits) lies in the LDS tail [tail0, kv_len) (host-checked, lds_tail);
   // the keys below tail0 are untouched this step, so their chunks load from
@@ -640,15 +653,26 @@ __global__ __launch_bounds__(64 * NW, 1) void attention_kernel(
           for (int i = 0; i < TV; ++i) {
             const int e = threadIdx.x + i * NT, dd = e / 4, s8 = (e % 4) * 8;
             if (dd < D && s8 < told) {
+              // (the piece that holds slot told - 1 may reach past kv_len:
+              // those slots as zeros, like the loop below writes them -- a
+              // cached value there would race with that loop's store)
+              const int nv = w.kv_len - tail0 - s8;  // >= 1 slots of the piece below kv_len
+              const uint32_t vw[4] = {tv[i].x, tv[i].y, tv[i].z, tv[i].w};
+              uint32_t mw[4];
+#pragma unroll
+              for (int k = 0; k < 4; ++k)
+                mw[k] = nv >= 2 * k + 2 ? vw[k] : nv == 2 * k + 1 ? vw[k] & 0xffffu : 0u;
               uint2 *dst = reinterpret_cast<uint2 *>(&sVt[dd][s8]);  // rows are 8-B aligned
-              dst[0] = make_uint2(tv[i].x, tv[i].y);
-              dst[1] = make_uint2(tv[i].z, tv[i].w);
+              dst[0] = make_uint2(mw[0], mw[1]);
+              dst[1] = make_uint2(mw[2], mw[3]);
             }
           }
           stamp(11);
           // keys past kv_len in the last chunk are masked, but P.V still
-          // multiplies their V by 0: zero them (as the cache's never-written
-          // slots are); a stored slot among them is written after the barrier
+          // multiplies their V by 0, and the cache may hold anything there
+          // (a recycled request slot: the last occupant's rows, a rejected
+          // tree's; 0 * Inf = NaN): they enter the product as zeros; a
+          // stored slot among them is written after the barrier
           for (int e = threadIdx.x; e < D * 32; e += NT) {
             const int dd = e >> 5, sl = w.kv_len - tail0 + (e & 31);
             if (sl < (nchunks - ctail) * 32) sVt[dd][sl] = 0;
@@ -796,8 +820,15 @@ __global__ __launch_bounds__(64 * NW, 1) void attention_kernel(
       continue;
     }
     h8 kf[2][KS], va[DT];
-    if (FUSED && c >= ctail) load_chunk_lds(c - ctail, kf, va);
-    else load_chunk(c, kf, va);
+    if (FUSED && c >= ctail) {
+      load_chunk_lds(c - ctail, kf, va);
+    } else {
+      load_chunk(c, kf, va);
+      // (not FUSED: the last chunk comes from memory, and past kv_len the
+      // cache may hold anything -- see the LDS tail's zeroing above; one
+      // wave-uniform branch per work item, off the other chunks' path)
+      if (!FUSED && c == nchunks - 1 && (w.kv_len & 31)) zero_past_kv_len(c * 32, va);
+    }
     compute_chunk(c * 32, kf, va);
   }
 
