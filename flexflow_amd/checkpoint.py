@@ -75,3 +75,59 @@ def llama_config_from_hf(src: Union[str, Mapping]) -> dict:
                    rope_high_freq_factor=float(sc["high_freq_factor"]),
                    rope_original_max_pos=int(sc["original_max_position_embeddings"]))
     return cfg
+
+
+_PEFT_PREFIX = "base_model.model.model."
+
+
+def convert_peft_adapter(state_dict: Mapping, adapter_config: Mapping, dst_folder: str,
+                         dtype=np.float16):
+    """Write an HF PEFT LoRA adapter in the reference's per-tensor format and
+    return ``(rank, alpha)``.
+
+    ``state_dict`` maps the PEFT keys
+    ``base_model.model.model.layers.{i}.mlp.down_proj.lora_{A,B}.weight`` (an
+    adapter name between ``lora_A`` and ``weight``, as in ``lora_A.default.
+    weight``, is dropped) to arrays or tensors; ``adapter_config`` is the
+    parsed ``adapter_config.json`` (``r``, ``lora_alpha``, ``target_modules``).
+    The files are named as the reference's loader reads them
+    (``layers.{i}.mlp.down_proj.lora_A.weight``, peft_weight_allocator.cc:
+    171-240), raw ``tofile`` of the HF row-major tensor, and the config is
+    copied next to them as ``adapter_config.json`` (``Model.load_lora(folder)``
+    takes rank and alpha from it).  Only ``down_proj`` is served: any other
+    target module, in the config or among the keys, raises ``ValueError``.
+    Needs no ``peft`` package."""
+    targets = adapter_config.get("target_modules") or []
+    if isinstance(targets, str):
+        targets = [targets]
+    bad = sorted(t for t in targets if t.split(".")[-1] != "down_proj")
+    if bad or not targets:
+        raise ValueError(f"convert_peft_adapter: only down_proj adapters are served, got {targets}")
+    if adapter_config.get("peft_type", "LORA") != "LORA":
+        raise ValueError(f"convert_peft_adapter: peft_type {adapter_config.get('peft_type')}")
+    rank, alpha = int(adapter_config["r"]), float(adapter_config["lora_alpha"])
+    tensors = {}
+    for key, val in state_dict.items():
+        if ".lora_" not in key:
+            continue
+        name = key[len(_PEFT_PREFIX):] if key.startswith(_PEFT_PREFIX) else key
+        parts = name.split(".")
+        # layers.{i}.mlp.down_proj.lora_A[.adapter].weight
+        if (len(parts) not in (6, 7) or parts[0] != "layers" or parts[2:4] != ["mlp", "down_proj"]
+                or parts[4] not in ("lora_A", "lora_B") or parts[-1] != "weight"):
+            raise ValueError(f"convert_peft_adapter: cannot serve adapter tensor {key}")
+        arr = val.detach().cpu().float().numpy() if hasattr(val, "detach") else np.asarray(val)
+        want = 0 if parts[4] == "lora_A" else 1
+        if arr.ndim != 2 or arr.shape[want] != rank:
+            raise ValueError(f"convert_peft_adapter: {key} has shape {arr.shape}, rank {rank}")
+        tensors[".".join(parts[:5] + ["weight"])] = arr
+    layers = {n.split(".")[1] for n in tensors}
+    if not tensors or any(f"layers.{i}.mlp.down_proj.lora_{ab}.weight" not in tensors
+                          for i in layers for ab in "AB"):
+        raise ValueError("convert_peft_adapter: lora_A / lora_B of down_proj missing")
+    os.makedirs(dst_folder, exist_ok=True)
+    for name, arr in tensors.items():
+        np.ascontiguousarray(arr, dtype=dtype).tofile(os.path.join(dst_folder, name))
+    with open(os.path.join(dst_folder, "adapter_config.json"), "w") as f:
+        json.dump(dict(adapter_config), f)
+    return rank, alpha

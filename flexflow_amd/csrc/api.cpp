@@ -70,13 +70,14 @@ extern "C" ffmi_status ffmi_batch_create(int max_tokens, int max_requests, ffmi_
   b->max_requests = max_requests;
   // header + tokens + work (<= tokens) + commits (<= tokens) + masks, and
   // room behind them for one float per token (a sampling model's draws) and
-  // one id per token (the targets of a model with logprobs on)
+  // two ids per token (the targets of a model with logprobs on, the adapter
+  // slots of a FFMI_MODEL_LORA model)
   b->cap = align16(sizeof(ffmi::BatchHeader)) + align16((size_t)max_tokens * sizeof(ffmi_token_info)) +
            align16((size_t)max_tokens * sizeof(ffmi::WorkDev)) +
            align16((size_t)max_tokens * sizeof(ffmi_commit_info)) +
            align16((size_t)max_requests * FFMI_MAX_TREE * sizeof(uint64_t)) + 64 +
            align16((size_t)max_tokens * sizeof(float)) +
-           align16((size_t)max_tokens * sizeof(int32_t));
+           2 * align16((size_t)max_tokens * sizeof(int32_t));
   // fine-grained (uncached on the device) and mapped: the model's first
   // kernel reads the step's blob straight from here (launch_rmsnorm's fetch)
   if (hipHostMalloc((void **)&b->host, b->cap, hipHostMallocCoherent | hipHostMallocMapped) !=
@@ -717,6 +718,22 @@ extern "C" ffmi_status ffmi_token_logprobs(const void *logits, int T, int V, flo
              FFMI_ERR_INVALID);
   FFMI_HIP(ffmi::launch_token_logprobs((const uint16_t *)logits, T, V, temperature, targets, picks,
                                        logprobs, workspace, (hipStream_t)stream));
+  return FFMI_OK;
+}
+
+extern "C" size_t ffmi_lora_workspace_bytes(int T, int F) {
+  return ffmi::lora_workspace_bytes(T, F);
+}
+
+extern "C" ffmi_status ffmi_lora_apply(const void *x, int T, int F, int H, const int32_t *slots,
+                                       const ffmi_lora_entry *table, void *y, int x_packed,
+                                       void *ws, size_t ws_bytes, void *h_out,
+                                       ffmi_stream stream) {
+  FFMI_CHECK(x && slots && table && y && T >= 0 && F > 0 && H > 0, FFMI_ERR_INVALID);
+  FFMI_CHECK(F % 32 == 0 && H % 8 == 0, FFMI_ERR_INVALID);
+  FFMI_CHECK(T == 0 || (ws && ws_bytes >= ffmi::lora_workspace_bytes(T, F)), FFMI_ERR_INVALID);
+  FFMI_HIP(ffmi::launch_lora((const uint16_t *)x, T, F, H, slots, table, (uint16_t *)y,
+                             x_packed != 0, (float *)ws, (uint16_t *)h_out, (hipStream_t)stream));
   return FFMI_OK;
 }
 

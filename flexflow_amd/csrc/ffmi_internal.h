@@ -264,6 +264,12 @@ size_t token_logprobs_workspace_bytes(int T, int V);
 hipError_t launch_token_logprobs(const uint16_t *logits, int T, int V, float temperature,
                                  const int32_t *targets, const int32_t *picks, float *logprobs,
                                  void *ws, hipStream_t s);
+// kernels/lora.hip: the LoRA update of a projection output in place, every row
+// by the adapter slots[t] names (include/ffmi.h ffmi_lora_apply)
+size_t lora_workspace_bytes(int T, int F);
+hipError_t launch_lora(const uint16_t *x, int T, int F, int H, const int32_t *slots,
+                       const ffmi_lora_entry *table, uint16_t *y, bool x_packed, float *ws,
+                       uint16_t *h_out, hipStream_t s);
 // Vocab-sharded tail (vshard_kernel): phase 0..2 write this rank's exchange
 // record ([P][T][W] floats, W >= max(4, 2k)); phase 3 merges into ids/probs.
 hipError_t launch_vshard(const uint16_t *logits, int T, int Vl, int P, int rank, int k,

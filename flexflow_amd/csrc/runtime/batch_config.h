@@ -2,7 +2,8 @@
 //
 // Same field names and meaning as include/flexflow/batch_config.h:53-240 of
 // the reference (so RequestManager logic and callers read the same), minus
-// Legion futures and the PEFT fields.  Capacities are compile-time like the
+// Legion futures and the PEFT fields other than the adapter a request names
+// (PerRequestInfo::lora_id; the reference's peft_model_id).  Capacities are compile-time like the
 // reference's MAX_NUM_* constants; MAX_NUM_TOKENS is raised to 2048 so that
 // max_tokens_per_batch = 1024 plus a full token tree per request fits the
 // verify batch (the reference's 1024 would overflow there).
@@ -47,6 +48,9 @@ class BatchConfig {
     int batch_config_request_id = -1;
     bool prompt_phase = false;
     RequestGuid request_guid = 0;
+    // the LoRA adapter an LLM with FFMI_MODEL_LORA applies to this request's
+    // rows (-1: none); the reference carries a PEFTModelID here.  Ours.
+    int lora_id = -1;
   };
   struct PerTokenInfo {
     int abs_depth_in_request = 0;

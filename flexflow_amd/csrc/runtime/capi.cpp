@@ -20,13 +20,42 @@ extern "C" ffmi_status ffmi_model_create(const ffmi_llama_config *cfg, const ffm
 extern "C" ffmi_status ffmi_model_create_ex(const ffmi_llama_config *cfg, const ffmi_model_opts *o,
                                             unsigned flags, ffmi_model **out) {
   if (!flags) return ffmi_model_create(cfg, o, out);
-  FFMI_CHECK(cfg && o && out && (flags & ~FFMI_MODEL_NATIVE_GQA) == 0, FFMI_ERR_INVALID);
+  FFMI_CHECK(cfg && o && out && (flags & ~(FFMI_MODEL_NATIVE_GQA | FFMI_MODEL_LORA)) == 0,
+             FFMI_ERR_INVALID);
+  if (flags & FFMI_MODEL_LORA) {
+    // SSMs run without adapters; the fp32 model has no LoRA kernels; under TP
+    // the reference shards A along F and adds before the all-reduce (not built)
+    const char *why = o->mode == FFMI_MODEL_BEAM ? "lora: a BEAM model (SSM) runs without adapters"
+                      : o->full_precision        ? "lora: fp16 models only (full_precision)"
+                      : o->tp_size > 1           ? "lora: tp_size > 1" : nullptr;
+    if (why) {
+      ffmi_set_last_error(why, __FILE__, __LINE__);
+      return FFMI_ERR_UNSUPPORTED;
+    }
+  }
   if (o->full_precision) {  // the fp32 model replicates K/V, as the reference does
     ffmi_set_last_error("native_gqa: fp16 models only (full_precision replicates K/V)", __FILE__,
                         __LINE__);
     return FFMI_ERR_UNSUPPORTED;
   }
   return ffmi::create_llama_gpu(cfg, o, out, flags);
+}
+
+extern "C" ffmi_status ffmi_model_lora_load(ffmi_model *m, int rank, float alpha, const void *A,
+                                            const void *B, int *id_out) {
+  if (!m || !id_out) return FFMI_ERR_INVALID;
+  return m->lora_load(rank, alpha, A, B, id_out);
+}
+
+extern "C" ffmi_status ffmi_model_lora_load_folder(ffmi_model *m, const char *folder, int rank,
+                                                   float alpha, int *id_out) {
+  if (!m || !folder || !id_out) return FFMI_ERR_INVALID;
+  return m->lora_load_folder(folder, rank, alpha, id_out);
+}
+
+extern "C" ffmi_status ffmi_model_lora_unload(ffmi_model *m, int id) {
+  if (!m) return FFMI_ERR_INVALID;
+  return m->lora_unload(id);
 }
 
 extern "C" size_t ffmi_model_kv_cache_bytes(ffmi_model *m) { return m ? m->kv_cache_bytes() : 0; }
@@ -189,6 +218,15 @@ extern "C" int64_t ffmi_rm_register_request(ffmi_rm *rm, const int *prompt, int 
   if (!rm || (n_prompt > 0 && !prompt) || n_prompt < 0) return 0;
   std::vector<int> p(prompt, prompt + n_prompt);
   return rm->rm.register_new_request(p, max_length, max_new_tokens, add_special_tokens != 0);
+}
+
+extern "C" int64_t ffmi_rm_register_request_ex(ffmi_rm *rm, const int *prompt, int n_prompt,
+                                               int max_length, int max_new_tokens,
+                                               int add_special_tokens, int lora_id) {
+  if (!rm || (n_prompt > 0 && !prompt) || n_prompt < 0 || lora_id < -1) return 0;
+  std::vector<int> p(prompt, prompt + n_prompt);
+  return rm->rm.register_new_request(p, max_length, max_new_tokens, add_special_tokens != 0,
+                                     lora_id);
 }
 
 extern "C" ffmi_status ffmi_rm_serve_incr_decoding(ffmi_rm *rm, ffmi_model *llm) {

@@ -70,6 +70,36 @@ struct HashModel : public ffmi_model {
 
   int slot_of(int r, int s) const { return r * slots + s; }
 
+  // LoRA adapters (model.h): an INC / TREE hash model "loads" an adapter by
+  // taking an id (no weights), and a row of a request that names adapter a >= 0
+  // folds a into its context hash -- the scheduler tests then see the id
+  // arrive with every row, and SpecInfer must still equal incremental decoding
+  ~HashModel() override { lora_id_release_all(this); }
+  ffmi_status lora_load(int rank, float alpha, const void *A, const void *B, int *id_out) override {
+    (void)alpha, (void)A, (void)B;
+    if (mode == FFMI_MODEL_BEAM) return ffmi_model::lora_load(rank, alpha, A, B, id_out);
+    if (!id_out || rank < 1) return FFMI_ERR_INVALID;
+    if (rank > FFMI_LORA_MAX_RANK) {
+      ffmi_set_last_error("lora: rank above FFMI_LORA_MAX_RANK", __FILE__, __LINE__);
+      return FFMI_ERR_UNSUPPORTED;
+    }
+    const int id = lora_id_acquire(this);
+    if (id < 0) return FFMI_ERR_OOM;
+    *id_out = id;
+    return FFMI_OK;
+  }
+  ffmi_status lora_unload(int id) override {
+    if (mode == FFMI_MODEL_BEAM) return ffmi_model::lora_unload(id);
+    return lora_id_release(this, id) ? FFMI_OK : FFMI_ERR_INVALID;
+  }
+  template <class BC>
+  static void fold_adapters(const BC &bc, std::vector<uint64_t> *hs) {
+    for (size_t t = 0; t < hs->size(); ++t) {
+      const int a = bc.requestsInfo[bc.tokensInfo[t].request_index].lora_id;
+      if (a >= 0) (*hs)[t] = mix64((*hs)[t] ^ (0xA0761D6478BD642Full * (uint64_t)(a + 1)));
+    }
+  }
+
   // returns context hash for each token; -1 entries poison the hash
   void contexts(const PackedStep &ps, std::vector<uint64_t> *hs) {
     for (const auto &c : ps.commits) {
@@ -136,6 +166,7 @@ struct HashModel : public ffmi_model {
     pack_inc(bc, max_requests, slots, &ps);
     std::vector<uint64_t> hs;
     contexts(ps, &hs);
+    fold_adapters(bc, &hs);
     fill_results(bc, hs, ir);
     return FFMI_OK;
   }
@@ -150,6 +181,7 @@ struct HashModel : public ffmi_model {
     pack_tree(bc, max_requests, slots, &ps);
     std::vector<uint64_t> hs;
     contexts(ps, &hs);
+    fold_adapters(bc, &hs);
     fill_results(bc, hs, ir);
     return FFMI_OK;
   }

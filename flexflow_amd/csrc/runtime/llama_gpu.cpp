@@ -12,6 +12,7 @@
 // (collective.hip) or RCCL, both in two column halves overlapped on a second
 // stream and captured in the step's HIP graph; norms replicated; lm_head
 // vocab-sharded with the sharded softmax / top-k tail (model.cc:3392-3419).
+#include <dirent.h>
 #include <stdio.h>
 #include <string.h>
 
@@ -181,6 +182,168 @@ struct LlamaGPU : public ffmi_model {
     *bytes += n;
     return FFMI_OK;
   }
+  // LoRA adapters on down_proj (FFMI_MODEL_LORA; lora_linear.cc): under the
+  // flag the down projection runs with its own reduce pass, outside the fused
+  // residual norms, and ffmi::launch_lora follows on proj.  Each row's adapter
+  // (BatchConfig::PerRequestInfo::lora_id of its request, -1 for an adapter
+  // this model did not load) rides the blob behind the records, the draws and
+  // the targets, so a replayed graph reads fresh assignments; a step none of
+  // whose rows has an adapter skips the launches (part of the graph key).
+  // Adapter storage and the device table [L][FFMI_LORA_MAX_ADAPTERS] are
+  // allocated at creation / load, never in a step.
+  bool lora = false;
+  ffmi_lora_entry *lora_tab = nullptr;
+  std::vector<ffmi_lora_entry> lora_tab_h;
+  uint16_t *lora_A[FFMI_LORA_MAX_ADAPTERS] = {}, *lora_B[FFMI_LORA_MAX_ADAPTERS] = {};
+  float *lora_ws = nullptr;
+  std::vector<int32_t> step_slots;
+  size_t step_slots_off = 0;
+  bool step_lora_any = false;
+  void take_step_slots(const BatchConfig &bc) {
+    step_slots.resize(bc.num_tokens);
+    step_lora_any = false;
+    for (int t = 0; t < bc.num_tokens; ++t) {
+      const int a = bc.requestsInfo[bc.tokensInfo[t].request_index].lora_id;
+      step_slots[t] = a >= 0 && a < FFMI_LORA_MAX_ADAPTERS && lora_A[a] ? a : -1;
+      step_lora_any = step_lora_any || step_slots[t] >= 0;
+    }
+  }
+  ffmi_status stage_step_slots(int T, size_t *bytes) {
+    step_slots_off = *bytes;
+    const size_t n = ((size_t)T * sizeof(int32_t) + 15) & ~(size_t)15;
+    FFMI_CHECK((int)step_slots.size() == T && *bytes + n <= batch->cap, FFMI_ERR_INVALID);
+    memcpy(batch->host + *bytes, step_slots.data(), (size_t)T * sizeof(int32_t));
+    *bytes += n;
+    return FFMI_OK;
+  }
+  ffmi_status lora_refuse(const char *why) {
+    ffmi_set_last_error(why, __FILE__, __LINE__);
+    return FFMI_ERR_UNSUPPORTED;
+  }
+  ffmi_status lora_load(int rank, float alpha, const void *A, const void *B, int *id_out) override {
+    if (!lora) return ffmi_model::lora_load(rank, alpha, A, B, id_out);
+    FFMI_CHECK(A && B && id_out && rank >= 1 && std::isfinite(alpha), FFMI_ERR_INVALID);
+    if (rank > FFMI_LORA_MAX_RANK) return lora_refuse("lora: rank above FFMI_LORA_MAX_RANK");
+    const int L = c.num_layers, F = Fl, H = c.hidden, R = FFMI_LORA_MAX_RANK;
+    // A as the packed activation tiles of a [R][F] matrix (one MFMA operand
+    // fragment per 16 ranks x 32 columns), B [H][R]; zero beyond the rank
+    const uint16_t *a = static_cast<const uint16_t *>(A), *b = static_cast<const uint16_t *>(B);
+    std::vector<uint16_t> ap((size_t)L * R * F, 0), bp((size_t)L * H * R, 0);
+    for (int l = 0; l < L; ++l) {
+      for (int j = 0; j < rank; ++j)
+        for (int k = 0; k < F; ++k)
+          ap[(size_t)l * R * F + act_packed_off(j, k, F)] = a[((size_t)l * rank + j) * F + k];
+      for (int n = 0; n < H; ++n)
+        memcpy(&bp[((size_t)l * H + n) * R], &b[((size_t)l * H + n) * rank], (size_t)rank * 2);
+    }
+    uint16_t *ad = nullptr, *bd = nullptr;
+    if (hipMalloc((void **)&ad, ap.size() * 2) != hipSuccess ||
+        hipMalloc((void **)&bd, bp.size() * 2) != hipSuccess) {
+      (void)hipFree(ad);
+      (void)hipGetLastError();
+      ffmi_set_last_error("lora: adapter alloc", __FILE__, __LINE__);
+      return FFMI_ERR_OOM;
+    }
+    const int id = lora_id_acquire(this);
+    if (id < 0) {
+      (void)hipFree(ad), (void)hipFree(bd);
+      ffmi_set_last_error("lora: FFMI_LORA_MAX_ADAPTERS adapters are loaded", __FILE__, __LINE__);
+      return FFMI_ERR_OOM;
+    }
+    const _Float16 s16 = (_Float16)(alpha / (float)rank);
+    for (int l = 0; l < L; ++l) {
+      ffmi_lora_entry &e = lora_tab_h[(size_t)l * FFMI_LORA_MAX_ADAPTERS + id];
+      e.A = ad + (size_t)l * R * F, e.B = bd + (size_t)l * H * R;
+      e.scale = (float)s16, e.rank = rank;
+    }
+    // (blocking copies; steps in flight read the table's other entries only)
+    const hipError_t e0 = hipStreamSynchronize(stream);
+    const hipError_t e1 = hipMemcpy(ad, ap.data(), ap.size() * 2, hipMemcpyHostToDevice);
+    const hipError_t e2 = hipMemcpy(bd, bp.data(), bp.size() * 2, hipMemcpyHostToDevice);
+    const hipError_t e3 = hipMemcpy(lora_tab, lora_tab_h.data(),
+                                    lora_tab_h.size() * sizeof(ffmi_lora_entry),
+                                    hipMemcpyHostToDevice);
+    lora_A[id] = ad, lora_B[id] = bd;
+    if (e0 != hipSuccess || e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) {
+      (void)lora_unload(id);
+      ffmi_set_last_error("lora: adapter upload", __FILE__, __LINE__);
+      return FFMI_ERR_HIP;
+    }
+    *id_out = id;
+    return FFMI_OK;
+  }
+  // one per-tensor file of the reference's adapter folder (fp16, or fp32
+  // converted round to nearest even, by file size as load_tensor)
+  ffmi_status lora_read(const std::string &path, size_t n, uint16_t *dst) {
+    FILE *f = fopen(path.c_str(), "rb");
+    if (!f) {
+      ffmi_set_last_error(("lora: adapter file not found: " + path).c_str(), __FILE__, __LINE__);
+      return FFMI_ERR_INVALID;
+    }
+    fseek(f, 0, SEEK_END);
+    const long bytes = ftell(f);
+    fseek(f, 0, SEEK_SET);
+    bool ok = false;
+    if (bytes == (long)(n * 2)) {
+      ok = fread(dst, 2, n, f) == n;
+    } else if (bytes == (long)(n * 4)) {
+      std::vector<float> h32(n);
+      ok = fread(h32.data(), 4, n, f) == n;
+      for (size_t i = 0; ok && i < n; ++i) {
+        const _Float16 v = (_Float16)h32[i];
+        memcpy(&dst[i], &v, 2);
+      }
+    }
+    fclose(f);
+    if (!ok) {
+      ffmi_set_last_error(("lora: adapter file has the wrong size: " + path).c_str(), __FILE__,
+                          __LINE__);
+      return FFMI_ERR_INVALID;
+    }
+    return FFMI_OK;
+  }
+  ffmi_status lora_load_folder(const char *folder, int rank, float alpha, int *id_out) override {
+    if (!lora) return ffmi_model::lora_load_folder(folder, rank, alpha, id_out);
+    FFMI_CHECK(rank >= 1, FFMI_ERR_INVALID);
+    if (rank > FFMI_LORA_MAX_RANK) return lora_refuse("lora: rank above FFMI_LORA_MAX_RANK");
+    // only down_proj is served: an adapter tensor of any other module refuses
+    if (DIR *dir = opendir(folder)) {
+      bool other = false;
+      while (const dirent *de = readdir(dir)) {
+        const std::string n = de->d_name;
+        if (n.find(".lora_") != std::string::npos && n.find(".mlp.down_proj.lora_") == std::string::npos)
+          other = true;
+      }
+      closedir(dir);
+      if (other) return lora_refuse("lora: the adapter targets a module other than down_proj");
+    }
+    const int L = c.num_layers, F = c.intermediate, H = c.hidden;
+    std::vector<uint16_t> a((size_t)L * rank * F), b((size_t)L * H * rank);
+    for (int l = 0; l < L; ++l) {
+      const std::string p = std::string(folder) + "/layers." + std::to_string(l) + ".mlp.down_proj.lora_";
+      ffmi_status st = lora_read(p + "A.weight", (size_t)rank * F, &a[(size_t)l * rank * F]);
+      if (st == FFMI_OK) st = lora_read(p + "B.weight", (size_t)H * rank, &b[(size_t)l * H * rank]);
+      if (st != FFMI_OK) return st;
+    }
+    return lora_load(rank, alpha, a.data(), b.data(), id_out);
+  }
+  ffmi_status lora_unload(int id) override {
+    if (!lora) return ffmi_model::lora_unload(id);
+    if (!lora_id_release(this, id)) {
+      ffmi_set_last_error("lora: not this model's adapter, or a registered request names it",
+                          __FILE__, __LINE__);
+      return FFMI_ERR_INVALID;
+    }
+    // no step reads the entries any more: clear them, then free the storage
+    for (int l = 0; l < c.num_layers; ++l)
+      lora_tab_h[(size_t)l * FFMI_LORA_MAX_ADAPTERS + id] = ffmi_lora_entry{};
+    FFMI_HIP(hipStreamSynchronize(stream));
+    FFMI_HIP(hipMemcpy(lora_tab, lora_tab_h.data(), lora_tab_h.size() * sizeof(ffmi_lora_entry),
+                       hipMemcpyHostToDevice));
+    (void)hipFree(lora_A[id]), (void)hipFree(lora_B[id]);
+    lora_A[id] = lora_B[id] = nullptr;
+    return FFMI_OK;
+  }
   // vocab-sharded lm_head at TP > 1 (model.cc:3392-3419): this rank's Vl rows
   // and the [P][Tm][kXW] exchange records of the sharded softmax / top-k
   int Vl = 0;
@@ -256,7 +419,7 @@ struct LlamaGPU : public ffmi_model {
 
   // ---- per-op profiling (HIP events on `stream`) ----
   enum Cat { GEMM_QKV, GEMM_O, GEMM_GATE_UP, GEMM_DOWN, GEMM_LM_HEAD, ATTENTION, NORM,
-             ALLREDUCE, SAMPLING, EMBED, LOGPROBS, NCAT };
+             ALLREDUCE, SAMPLING, EMBED, LOGPROBS, LORA, NCAT };
   struct ProfRec {
     int cat;
     hipEvent_t a, b;
@@ -332,7 +495,7 @@ struct LlamaGPU : public ffmi_model {
     static const char *names[NCAT] = {"gemm_qkv", "gemm_o_proj", "gemm_gate_up_silu",
                                       "gemm_down", "gemm_lm_head", "attention", "rmsnorm",
                                       "rowpar_gemm_allreduce", "softmax_argmax", "embedding",
-                                      "token_logprobs"};
+                                      "token_logprobs", "lora"};
     int n = 0;
     for (int i = 0; i < NCAT; ++i) {
       if (opstat[i].launches == 0) continue;
@@ -556,6 +719,8 @@ struct LlamaGPU : public ffmi_model {
       if (e) (void)hipEventDestroy(e);
     if (chain_t0) (void)hipEventDestroy(chain_t0);
     clear_graphs();
+    lora_id_release_all(this);
+    for (int i = 0; i < FFMI_LORA_MAX_ADAPTERS; ++i) (void)hipFree(lora_A[i]), (void)hipFree(lora_B[i]);
     for (auto &L : layers) ffmi_attn_destroy(L.attn);
     for (auto e : ev_pool) (void)hipEventDestroy(e);
     for (auto e : ev_chunk) (void)hipEventDestroy(e);
@@ -681,6 +846,12 @@ struct LlamaGPU : public ffmi_model {
     TRY(alloc(&ss_o, (size_t)2 * 32 * (H / 16)));
     ss_d = ss_o + (size_t)32 * (H / 16);
     TRY(alloc(&mlp, (size_t)Tm * Fl));
+    if (lora) {
+      lora_tab_h.assign((size_t)c.num_layers * FFMI_LORA_MAX_ADAPTERS, ffmi_lora_entry{});
+      TRY(alloc(&lora_tab, lora_tab_h.size()));
+      FFMI_HIP(hipMemset(lora_tab, 0, lora_tab_h.size() * sizeof(ffmi_lora_entry)));
+      TRY(alloc(&lora_ws, (ffmi::lora_workspace_bytes(Tm, Fl) + 3) / 4));
+    }
     // (a GQA handle does not fold the o projection in: the GEMM runs)
     fuse_ao = !native_gqa && P == 1 && d == 64 && H <= 1024 && H % 16 == 0 &&
               !(getenv("FFMI_FUSE_AO") && atoi(getenv("FFMI_FUSE_AO")) == 0);
@@ -990,9 +1161,11 @@ struct LlamaGPU : public ffmi_model {
   struct GraphKey {
     int T, W, C, k, parity, overlap, fused, max_q, slot;
     size_t bytes;
+    int lora_any = 0;  // (FFMI_MODEL_LORA: a row of the step has an adapter)
     bool operator<(const GraphKey &o) const {
-      return std::tie(T, W, C, k, parity, overlap, fused, max_q, slot, bytes) <
-             std::tie(o.T, o.W, o.C, o.k, o.parity, o.overlap, o.fused, o.max_q, o.slot, o.bytes);
+      return std::tie(T, W, C, k, parity, overlap, fused, max_q, slot, bytes, lora_any) <
+             std::tie(o.T, o.W, o.C, o.k, o.parity, o.overlap, o.fused, o.max_q, o.slot, o.bytes,
+                      o.lora_any);
     }
   };
   // TREE steps write alternate halves of the attention staging (commits of
@@ -1070,6 +1243,7 @@ struct LlamaGPU : public ffmi_model {
     if (T == 0) return FFMI_OK;
     if (sampling && (st = stage_step_u(T, &bytes)) != FFMI_OK) return st;
     if (logprobs && (st = stage_step_targets(T, &bytes)) != FFMI_OK) return st;
+    if (lora && (st = stage_step_slots(T, &bytes)) != FFMI_OK) return st;
     probs_h = reinterpret_cast<float *>(ids_h + cur_slot * slot_ints() + (size_t)T * k);
     // graphed: small steps, and tree-verify steps of one work item per
     // request (a fixed shape while the batch is full: T = 168 for 8 requests
@@ -1082,7 +1256,7 @@ struct LlamaGPU : public ffmi_model {
       const GraphKey key{T, batch->num_work, batch->num_commits, k, tree_parity,
                          batch->commit_overlap ? 1 : 0,
                          (batch->one_item_per_req ? 1 : 0) | (batch->lds_tail ? 2 : 0),
-                         batch->max_q, cur_slot, bytes};
+                         batch->max_q, cur_slot, bytes, lora && step_lora_any ? 1 : 0};
       auto it = graphs.find(key);
       if (it == graphs.end()) {
         if (graphs.size() >= 512) clear_graphs();
@@ -1232,6 +1406,13 @@ struct LlamaGPU : public ffmi_model {
     int mark_i = 0;
     const bool fuse = (fuse_norms == 2 || (fuse_norms == 1 && H >= 2048)) && !dbg &&
                       o.tp_size == 1 && T <= 32 && H % 32 == 0 && Hl % 32 == 0 && H <= 4096;
+    // (FFMI_MODEL_LORA, a step with an adapter on some row: down runs unfused
+    // and its split-K slabs are reduced into proj for the update, so the norm
+    // after it -- the next layer's attention norm, the final norm -- is a
+    // launch again; o and gate/up keep their fused pair.  A step without
+    // adapters is the step of a model without the flag)
+    const bool lora_step = lora && step_lora_any;
+    const bool fuse_d = fuse && !lora_step;
     // the residual norms inside the transport's all-reduces (tp_fuse_norm)
     const bool arn = peer && !solo && o.tp_size > 1 && (tp_fuse_norm == 2 || (tp_fuse_norm == 1 && !dbg));
     for (int l = 0; l < c.num_layers; ++l) {
@@ -1252,7 +1433,7 @@ struct LlamaGPU : public ffmi_model {
       // fused residual norms (see fuse_norms): from layer 1 on, the attention
       // norm is the qkv GEMM's prologue on the residual the down projection
       // left, and every post-attention norm the gate/up GEMM's
-      const bool fz_in = fuse && l > 0;
+      const bool fz_in = fuse_d && l > 0;
       ffmi::FuseArgs fz_qkv, fz_o, fz_gu, fz_d;
       if (fuse) {
         fz_o.kind = fz_d.kind = 1;
@@ -1350,7 +1531,7 @@ struct LlamaGPU : public ffmi_model {
       prof_end(pr, GEMM_GATE_UP, gemm_bytes(T, 2 * Fl, Fl, H), 2.0 * T * 2 * Fl * H);
       mk();
       if (dbg) TRY(dbg_copy(FFMI_DBG_MLP_ACT, l, mlp, T));
-      if (fuse) {  // down projection + residual add (+ sums of squares)
+      if (fuse_d) {  // down projection + residual add (+ sums of squares)
         pr = prof_begin(on);
         FFMI_HIP(ffmi::launch_gemm(mlp, L.wd, res, (float *)ws, ws_bytes, T, H, Fl, XP, stream,
                                    nullptr, 0, &fz_d));
@@ -1362,6 +1543,21 @@ struct LlamaGPU : public ffmi_model {
         FFMI_HIP(ffmi::launch_gemm(mlp, L.wd, proj, (float *)ws, ws_bytes, T, H, Fl, XP, stream,
                                    H <= 8192 ? &down_part : nullptr));
         prof_end(pr, GEMM_DOWN, gemm_bytes(T, H, H, Fl), 2.0 * T * H * Fl);
+        if (lora_step) {  // proj += scale * (mlp A^T) B^T on the rows with an adapter
+          pr = prof_begin(on);
+          // (the slabs summed in slab order and rounded once: the fp16 value
+          // every consumer of the slabs computes, so rows without an adapter
+          // keep the bits of a step without adapters)
+          if (down_part.S > 0) {
+            FFMI_HIP(ffmi::launch_partials_reduce(down_part, proj, T, H, stream));
+            down_part = ffmi::Partials();
+          }
+          FFMI_HIP(ffmi::launch_lora(mlp, T, Fl, H,
+                                     reinterpret_cast<const int32_t *>(batch->dev + step_slots_off),
+                                     lora_tab + (size_t)l * FFMI_LORA_MAX_ADAPTERS, proj, packed,
+                                     lora_ws, nullptr, stream));
+          prof_end(pr, LORA, 2.0 * FFMI_LORA_MAX_RANK * ((double)Fl + H) + 4.0 * T * H, 0);
+        }
         mk();
         mk();  // (two back to back: the marker-to-marker boundary itself)
       } else {
@@ -1386,7 +1582,7 @@ struct LlamaGPU : public ffmi_model {
     };
     if (!arn) {  // (arn: the last down all-reduce applied the final norm)
       pr = prof_begin(ptail);
-      if (fuse)  // res already holds the last residual add
+      if (fuse_d)  // res already holds the last residual add
         FFMI_HIP(ffmi::launch_rmsnorm(res, nullptr, final_norm, nullptr, h, T, H, eps, stream, packed));
       else
         FFMI_HIP(ffmi::launch_rmsnorm(res, proj, final_norm, res, h, T, H, eps, stream, packed,
@@ -1482,6 +1678,7 @@ struct LlamaGPU : public ffmi_model {
     pack_inc(bc, o.max_requests, slots, &ps);
     if (sampling) draw_step_u(bc);
     if (logprobs) take_step_targets(bc);
+    if (lora) take_step_slots(bc);
     cur_slot = 0;
     ffmi_status st = forward(1);
     if (st != FFMI_OK) return st;
@@ -1494,6 +1691,7 @@ struct LlamaGPU : public ffmi_model {
     FFMI_CHECK(bc.num_tokens <= o.max_tokens, FFMI_ERR_INVALID);
     pack_tree(bc, o.max_requests, slots, &ps);
     if (logprobs) take_step_targets(bc);
+    if (lora) take_step_slots(bc);
     cur_slot = 0;
     ffmi_status st = forward(1);
     if (st != FFMI_OK) return st;
@@ -1644,6 +1842,12 @@ ffmi_status create_llama_gpu(const ffmi_llama_config *cfg, const ffmi_model_opts
   m->c = *cfg;
   m->o = *o;
   m->native_gqa = (flags & FFMI_MODEL_NATIVE_GQA) != 0;
+  m->lora = (flags & FFMI_MODEL_LORA) != 0;
+  if (m->lora && (o->mode == FFMI_MODEL_BEAM || o->tp_size > 1)) {
+    delete m;
+    ffmi_set_last_error("lora: INC / TREE models at tp_size 1", __FILE__, __LINE__);
+    return FFMI_ERR_UNSUPPORTED;
+  }
   if (o->weights_folder && o->weights_folder[0]) m->weights_folder = o->weights_folder;
   m->o.weights_folder = nullptr;
   ffmi_status st = m->init();

@@ -146,6 +146,24 @@ struct ffmi_model {
     (void)arg;
     return FFMI_ERR_UNSUPPORTED;
   }
+  // LoRA adapters (ffmi_model_lora_load / _unload; A [L][rank][F], B
+  // [L][H][rank] fp16 on the host): only a model created with FFMI_MODEL_LORA
+  // serves them
+  virtual ffmi_status lora_load(int rank, float alpha, const void *A, const void *B, int *id_out) {
+    (void)rank, (void)alpha, (void)A, (void)B, (void)id_out;
+    ffmi_set_last_error("lora: the model was not created with FFMI_MODEL_LORA", __FILE__, __LINE__);
+    return FFMI_ERR_UNSUPPORTED;
+  }
+  virtual ffmi_status lora_load_folder(const char *folder, int rank, float alpha, int *id_out) {
+    (void)folder, (void)rank, (void)alpha, (void)id_out;
+    ffmi_set_last_error("lora: the model was not created with FFMI_MODEL_LORA", __FILE__, __LINE__);
+    return FFMI_ERR_UNSUPPORTED;
+  }
+  virtual ffmi_status lora_unload(int id) {
+    (void)id;
+    ffmi_set_last_error("lora: the model was not created with FFMI_MODEL_LORA", __FILE__, __LINE__);
+    return FFMI_ERR_UNSUPPORTED;
+  }
   // bytes of the K plus V caches of every layer's attention handle
   virtual size_t kv_cache_bytes() const { return 0; }
   virtual long debug_width(int which) const {
@@ -155,6 +173,15 @@ struct ffmi_model {
 };
 
 namespace ffmi {
+// Process-wide LoRA adapter ids (0 .. FFMI_LORA_MAX_ADAPTERS - 1), the
+// reference's PEFTModelID registry: a model takes an id when it loads an
+// adapter, requests naming it hold references (RequestManager), and the id is
+// given back only by its owner and only with no reference left.
+int lora_id_acquire(const void *owner);               // -1: none free
+bool lora_id_release(const void *owner, int id);      // false: not the owner's, or referenced
+void lora_id_release_all(const void *owner);          // (a model going away)
+bool lora_id_loaded(int id);
+void lora_id_ref(int id, int delta);
 ffmi_status create_llama_gpu(const ffmi_llama_config *cfg, const ffmi_model_opts *o,
                              ffmi_model **out, unsigned flags = 0);  // (FFMI_MODEL_* bits)
 // full precision (--use-full-precision): runtime/llama_f32.cpp

@@ -25,6 +25,7 @@
 #include <chrono>
 #include <map>
 #include <memory>
+#include <mutex>
 
 void ffmi_set_last_error(const char *msg, const char *file, int line);  // api.cpp
 
@@ -62,6 +63,61 @@ int BatchConfig::num_active_requests() const {
 
 RequestManager::RequestManager() {}
 
+RequestManager::~RequestManager() {
+  for (const auto &kv : all_requests)
+    if (kv.second.lora_id >= 0 && kv.second.status != Request::COMPLETED)
+      lora_id_ref(kv.second.lora_id, -1);
+}
+
+// ---- process-wide LoRA adapter ids (model.h) ----
+namespace {
+struct LoraIds {
+  std::mutex mu;
+  const void *owner[FFMI_LORA_MAX_ADAPTERS] = {};
+  int refs[FFMI_LORA_MAX_ADAPTERS] = {};
+};
+LoraIds &lora_ids() {
+  static LoraIds g;
+  return g;
+}
+}  // namespace
+int lora_id_acquire(const void *owner) {
+  LoraIds &g = lora_ids();
+  std::lock_guard<std::mutex> lk(g.mu);
+  for (int i = 0; i < FFMI_LORA_MAX_ADAPTERS; ++i)
+    if (!g.owner[i]) {
+      g.owner[i] = owner;
+      g.refs[i] = 0;
+      return i;
+    }
+  return -1;
+}
+bool lora_id_release(const void *owner, int id) {
+  LoraIds &g = lora_ids();
+  std::lock_guard<std::mutex> lk(g.mu);
+  if (id < 0 || id >= FFMI_LORA_MAX_ADAPTERS || g.owner[id] != owner || g.refs[id] > 0)
+    return false;
+  g.owner[id] = nullptr;
+  return true;
+}
+void lora_id_release_all(const void *owner) {
+  LoraIds &g = lora_ids();
+  std::lock_guard<std::mutex> lk(g.mu);
+  for (int i = 0; i < FFMI_LORA_MAX_ADAPTERS; ++i)
+    if (g.owner[i] == owner) g.owner[i] = nullptr, g.refs[i] = 0;
+}
+bool lora_id_loaded(int id) {
+  LoraIds &g = lora_ids();
+  std::lock_guard<std::mutex> lk(g.mu);
+  return id >= 0 && id < FFMI_LORA_MAX_ADAPTERS && g.owner[id] != nullptr;
+}
+void lora_id_ref(int id, int delta) {
+  LoraIds &g = lora_ids();
+  std::lock_guard<std::mutex> lk(g.mu);
+  if (id >= 0 && id < FFMI_LORA_MAX_ADAPTERS && g.owner[id])
+    g.refs[id] = std::max(0, g.refs[id] + delta);
+}
+
 void RequestManager::apply_limits() const {
   g_limits.max_requests_per_batch = max_requests_per_batch;
   g_limits.max_tokens_per_batch = max_tokens_per_batch;
@@ -95,8 +151,10 @@ bool RequestManager::push_spec_infer_tree_width(int w) {
 // request_manager.cc:334-441 (tokenizer replaced by token ids)
 RequestManager::RequestGuid RequestManager::register_new_request(
     const std::vector<int> &prompt, int max_length, int max_new_tokens,
-    bool add_special_tokens) {
+    bool add_special_tokens, int lora_id) {
+  if (lora_id != -1 && !lora_id_loaded(lora_id)) return 0;
   Request request;
+  request.lora_id = lora_id;
   request.status = Request::PENDING;
   request.guid = next_available_guid++;
   request.max_length = max_length;
@@ -112,6 +170,7 @@ RequestManager::RequestGuid RequestManager::register_new_request(
   if (request.max_length >= max_sequence_length) return 0;
   request.tokens.insert(request.tokens.end(), prompt.begin(), prompt.end());
   request.initial_len = (int)request.tokens.size();
+  if (lora_id >= 0) lora_id_ref(lora_id, +1);
   if (!ssm_models.empty()) request.beam_trees.resize(ssm_models.size());
   pending_infr_request_queue.push_back(request);
   all_requests[request.guid] = request;
@@ -141,6 +200,7 @@ bool RequestManager::check_inf_req_completion(const BatchConfig &old_bc, int i) 
 
 void RequestManager::complete_request(Request &request, bool spec) {
   request.status = Request::COMPLETED;
+  if (request.lora_id >= 0) lora_id_ref(request.lora_id, -1);
   GenerationResult &gr = request_generation_results[request.guid];
   gr.output_tokens = request.tokens;
   // one value per output token: what lay beyond the tokens (a dropped EOS,
@@ -241,6 +301,7 @@ BatchConfig RequestManager::prepare_next_batch(const BatchConfig &old_bc,
     R.first_token_depth_in_request = processed;
     R.first_token_offset_in_batch = new_bc.num_tokens;
     R.request_guid = old_bc.requestsInfo[i].request_guid;
+    R.lora_id = lora_id_of(R.request_guid);
     R.max_length = old_bc.requestsInfo[i].max_length;
     num_active_req++;
     new_bc.requestsInfo[num_active_req].batch_config_request_id = i;
@@ -281,6 +342,7 @@ BatchConfig RequestManager::prepare_next_batch(const BatchConfig &old_bc,
     R.first_token_depth_in_request = 0;
     R.first_token_offset_in_batch = new_bc.num_tokens;
     R.request_guid = new_request.guid;
+    R.lora_id = lora_id_of(R.request_guid);
     R.num_tokens_in_batch = std::min(max_tokens_per_batch - new_bc.num_tokens,
                                      (int)new_request.tokens.size());
     R.max_length = new_request.max_length;
@@ -372,6 +434,7 @@ BeamSearchBatchConfig RequestManager::prepare_next_batch_init(
         R.first_token_depth_in_request = verified_tokens.front().second;
         R.first_token_offset_in_batch = new_bc.num_tokens;
         R.request_guid = guid;
+        R.lora_id = lora_id_of(R.request_guid);
         R.max_length = old_bc.requestsInfo[i].max_length;
         R.num_tokens_in_batch = (int)verified_tokens.size();
         new_bc.requestsInfo[num_active_req].batch_config_request_id = i;
@@ -421,6 +484,7 @@ BeamSearchBatchConfig RequestManager::prepare_next_batch_init(
       R.first_token_depth_in_request = request.ssm_cache_size;
       R.first_token_offset_in_batch = new_bc.num_tokens;
       R.request_guid = guid;
+      R.lora_id = lora_id_of(R.request_guid);
       R.max_length = old_bc.requestsInfo[i].max_length;
       R.num_tokens_in_batch = 0;
       new_bc.requestsInfo[num_active_req].batch_config_request_id = i;
@@ -450,6 +514,7 @@ BeamSearchBatchConfig RequestManager::prepare_next_batch_init(
     R.first_token_depth_in_request = 0;
     R.first_token_offset_in_batch = new_bc.num_tokens;
     R.request_guid = new_request.guid;
+    R.lora_id = lora_id_of(R.request_guid);
     R.num_tokens_in_batch =
         std::min(max_tokens_per_batch - new_bc.num_tokens, (int)new_request.tokens.size());
     R.max_length = new_request.max_length;
@@ -512,6 +577,7 @@ BeamSearchBatchConfig RequestManager::prepare_next_batch_beam(
     R.first_token_depth_in_request = processed;
     R.first_token_offset_in_batch = new_bc.num_tokens;
     R.request_guid = old_bc.requestsInfo[i].request_guid;
+    R.lora_id = lora_id_of(R.request_guid);
     R.max_length = old_bc.requestsInfo[i].max_length;
     ++profiling_requests[request.guid].ssm_decoding_steps;
     // the reference indexes the widths by ssm_decoding_steps, reset to 0 at
@@ -561,6 +627,7 @@ BeamSearchBatchConfig RequestManager::prepare_next_batch_beam(
     R.first_token_depth_in_request = processed;
     R.first_token_offset_in_batch = new_bc.num_tokens;
     R.request_guid = old_bc.requestsInfo[i].request_guid;
+    R.lora_id = lora_id_of(R.request_guid);
     R.max_length = old_bc.requestsInfo[i].max_length;
     new_bc.requestsInfo[num_active_req].batch_config_request_id = i;
     B.beam_size = 1;
@@ -657,6 +724,7 @@ TreeVerifyBatchConfig RequestManager::prepare_next_batch_verify(
       R.first_token_depth_in_request = tree.front().second;
       R.first_token_offset_in_batch = new_bc.num_tokens;
       R.request_guid = guid;
+      R.lora_id = lora_id_of(R.request_guid);
       R.max_length = b0.requestsInfo[i].max_length;
       new_bc.requestsInfo[num_active_req].batch_config_request_id = i;
       new_bc.causalMask[i] = b0.causalMask[i];
@@ -730,6 +798,7 @@ TreeVerifyBatchConfig RequestManager::prepare_next_batch_verify(
       R.first_token_depth_in_request = request.llm_cache_size;
       R.first_token_offset_in_batch = new_bc.num_tokens;
       R.request_guid = guid;
+      R.lora_id = lora_id_of(R.request_guid);
       R.max_length = b0.requestsInfo[i].max_length;
       new_bc.requestsInfo[num_active_req].batch_config_request_id = i;
       new_bc.request_completed[i] = false;

@@ -26,6 +26,7 @@ struct Request {
   int max_length = -1;
   int max_new_tokens = -1;
   bool add_special_tokens = true;
+  int lora_id = -1;  // LoRA adapter the LLM applies to this request's rows (-1: none)
   int initial_len = 0;
   int ssm_cache_size = 0;
   int llm_cache_size = 0;
@@ -59,6 +60,7 @@ class RequestManager {
   using TokenDepth = std::pair<TokenId, int>;
 
   RequestManager();
+  ~RequestManager();  // (drops the adapter references of unfinished requests)
   void set_max_requests_per_batch(int n) { max_requests_per_batch = n; }
   void set_max_tokens_per_batch(int n) { max_tokens_per_batch = n; }
   void set_max_spec_tree_token_num(int n) { max_spec_tree_token_num = n; }
@@ -116,8 +118,11 @@ class RequestManager {
   void set_old_llama_tokenizer(bool v) { old_llama_tokenizer = v; }
   void set_verbose(bool v) { verbose = v; }
 
+  // lora_id: -1, or a loaded adapter (lora_id_loaded), which the request holds
+  // a reference on until it completes; an id that is not loaded returns 0
   RequestGuid register_new_request(const std::vector<int> &prompt, int max_length,
-                                   int max_new_tokens, bool add_special_tokens);
+                                   int max_new_tokens, bool add_special_tokens,
+                                   int lora_id = -1);
 
   // bitmask helpers (request_manager.cc:2382-2517)
   void initBitMask(BatchConfig::BitMask &bitmask, int initLength);
@@ -201,6 +206,10 @@ class RequestManager {
   int score_id_of(const Request &request, int depth) const {
     return record_logprobs && depth + 1 < (int)request.tokens.size() ? request.tokens[depth + 1]
                                                                      : -1;
+  }
+  int lora_id_of(RequestGuid guid) const {
+    auto it = all_requests.find(guid);
+    return it == all_requests.end() ? -1 : it->second.lora_id;
   }
   static void set_logprob(Request &request, int pos, float lp) {
     if ((int)request.logprobs.size() <= pos) request.logprobs.resize((size_t)pos + 1, 0.f);

@@ -37,6 +37,8 @@ FAULT_NONE, FAULT_ROPE_POS, FAULT_RESID_ROUND, FAULT_TP_HEAD_SWAP, FAULT_TP_AR_D
 SPEC_EXT_WIDTH4, SPEC_EXT_MULTI_SSM = 1, 2
 # ffmi_model_create_ex flags (include/ffmi.h FFMI_MODEL_*)
 MODEL_NATIVE_GQA = 1
+MODEL_LORA = 4  # (2 is left unassigned: it stays an invalid flag)
+LORA_MAX_ADAPTERS, LORA_MAX_RANK = 8, 64
 # ffmi_attn_set_gqa_route
 GQA_ROUTE_AUTO, GQA_ROUTE_KV_INDEXED, GQA_ROUTE_GROUP_SHARED = 0, 1, 2
 ATTN_QTILE = 32
@@ -97,6 +99,11 @@ class ModelOpts(ctypes.Structure):
                 ("max_tree_tokens", c_int), ("weight_seed", c_uint64), ("use_graphs", c_int),
                 ("weights_folder", ctypes.c_char_p), ("weight_init", c_int),
                 ("full_precision", c_int)]
+
+
+class LoraEntry(ctypes.Structure):
+    """ffmi_lora_entry: one adapter of ffmi_lora_apply's table."""
+    _fields_ = [("A", c_void_p), ("B", c_void_p), ("scale", c_float), ("rank", c_int)]
 
 
 class RMConfig(ctypes.Structure):
@@ -195,6 +202,16 @@ SIGNATURES = {
     "ffmi_fill_weight": (c_int, [c_void_p, c_size_t, ctypes.c_char_p, c_uint64, c_int, c_void_p]),
     "ffmi_model_create_ex": (c_int, [ctypes.POINTER(LlamaConfig), ctypes.POINTER(ModelOpts),
                                      ctypes.c_uint, ctypes.POINTER(c_void_p)]),
+    "ffmi_model_lora_load": (c_int, [c_void_p, c_int, c_float, c_void_p, c_void_p,
+                                     ctypes.POINTER(c_int)]),
+    "ffmi_model_lora_load_folder": (c_int, [c_void_p, ctypes.c_char_p, c_int, c_float,
+                                            ctypes.POINTER(c_int)]),
+    "ffmi_model_lora_unload": (c_int, [c_void_p, c_int]),
+    "ffmi_lora_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "ffmi_lora_apply": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
+                                c_void_p, c_size_t, c_void_p, c_void_p]),
+    "ffmi_rm_register_request_ex": (c_int64, [c_void_p, ctypes.POINTER(c_int), c_int, c_int, c_int,
+                                              c_int, c_int]),
     "ffmi_model_kv_cache_bytes": (c_size_t, [c_void_p]),
     "ffmi_model_create": (c_int, [ctypes.POINTER(LlamaConfig), ctypes.POINTER(ModelOpts),
                                   ctypes.POINTER(c_void_p)]),

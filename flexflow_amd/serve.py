@@ -36,7 +36,7 @@ class Model:
                  tp_size=1, comm=None, weights_folder: Optional[str] = None,
                  weight_init: Union[int, str] = 0, full_precision: bool = False,
                  generation_config: Optional[GenerationConfig] = None, sampling_seed: int = 0,
-                 native_gqa: bool = False, logprobs: bool = False):
+                 native_gqa: bool = False, logprobs: bool = False, lora: bool = False):
         """weights_folder: a checkpoint in the reference's per-tensor format
         (see checkpoint.convert_hf_model); None: seeded synthetic weights,
         `weight_init` "uniform" (0, the bench's), "depth_scaled" (1) or
@@ -46,7 +46,9 @@ class Model:
         see set_sampling (None: greedy decoding).  native_gqa: K/V projections
         and the KV cache at num_kv_heads instead of replicated to every query
         head (FFMI_MODEL_NATIVE_GQA; fp16, num_kv_heads % tp_size == 0).
-        logprobs: see set_logprobs."""
+        logprobs: see set_logprobs.  lora: the model serves LoRA adapters on
+        down_proj (FFMI_MODEL_LORA; see load_lora): fp16 "inc" / "tree" models
+        at tp_size 1."""
         L = F.lib()
         self.config = dict(config)
         self.mode = mode
@@ -57,7 +59,8 @@ class Model:
                            F.WEIGHT_INITS.get(weight_init, weight_init), int(full_precision))
         h = ctypes.c_void_p()
         F.check(L.ffmi_model_create_ex(ctypes.byref(cfg), ctypes.byref(opts),
-                                       F.MODEL_NATIVE_GQA if native_gqa else 0, ctypes.byref(h)),
+                                       (F.MODEL_NATIVE_GQA if native_gqa else 0) |
+                                       (F.MODEL_LORA if lora else 0), ctypes.byref(h)),
                 "ffmi_model_create")
         self.handle = h
         if generation_config is not None:
@@ -92,6 +95,48 @@ class Model:
         full_precision model and a vocab-sharded lm_head
         (ffmi_model_set_logprobs)."""
         F.check(F.lib().ffmi_model_set_logprobs(self.handle, int(bool(enable))), "set_logprobs")
+
+    def load_lora(self, A, B=None, alpha: Optional[float] = None, rank: Optional[int] = None) -> int:
+        """Load a LoRA adapter of every layer's down_proj and return its id
+        (ffmi_model_lora_load; at most F.LORA_MAX_ADAPTERS at a time, rank <=
+        F.LORA_MAX_RANK).  Either arrays, load_lora(A, B, alpha) with A
+        [num_layers][rank][intermediate] and B [num_layers][hidden][rank] as
+        HF PEFT stores lora_A.weight / lora_B.weight (cast to fp16), or a
+        folder in the reference's per-tensor format, load_lora(folder) --
+        rank and alpha then come from the folder's adapter_config.json, which
+        checkpoint.convert_peft_adapter writes, unless given.  A request names
+        the id at registration (register_new_request(..., lora_id=id))."""
+        import numpy as np
+        out = ctypes.c_int(-1)
+        if isinstance(A, (str, os.PathLike)):
+            folder = os.fspath(A)
+            if rank is None or alpha is None:
+                import json
+                with open(os.path.join(folder, "adapter_config.json")) as f:
+                    ac = json.load(f)
+                rank = ac["r"] if rank is None else rank
+                alpha = ac["lora_alpha"] if alpha is None else alpha
+            F.check(F.lib().ffmi_model_lora_load_folder(self.handle, folder.encode(), int(rank),
+                                                        float(alpha), ctypes.byref(out)),
+                    "load_lora")
+            return out.value
+        A = np.ascontiguousarray(np.asarray(A, dtype=np.float16))
+        B = np.ascontiguousarray(np.asarray(B, dtype=np.float16))
+        c = self.config
+        r = A.shape[1] if A.ndim == 3 else -1
+        if A.shape != (c["num_layers"], r, c["intermediate"]) or \
+                B.shape != (c["num_layers"], c["hidden"], r):
+            raise ValueError(f"load_lora: A {A.shape} / B {B.shape} do not fit the model")
+        F.check(F.lib().ffmi_model_lora_load(self.handle, r, float(r if alpha is None else alpha),
+                                             A.ctypes.data_as(ctypes.c_void_p),
+                                             B.ctypes.data_as(ctypes.c_void_p), ctypes.byref(out)),
+                "load_lora")
+        return out.value
+
+    def unload_lora(self, lora_id: int):
+        """Free an adapter of this model (ffmi_model_lora_unload); FFMIError
+        while a registered, unfinished request names it."""
+        F.check(F.lib().ffmi_model_lora_unload(self.handle, int(lora_id)), "unload_lora")
 
     def set_profiling(self, level: int):
         F.check(F.lib().ffmi_model_set_profiling(self.handle, level), "set_profiling")
@@ -363,7 +408,7 @@ class RequestManager:
 
     def register_new_request(self, prompt: Union[str, List[int], None], max_length=-1,
                              max_new_tokens=-1, add_special_tokens=True,
-                             benchmarking_tokens=-1) -> int:
+                             benchmarking_tokens=-1, lora_id=-1) -> int:
         """Token ids, or text encoded by the registered tokenizer without
         special tokens (request_manager.cc:369-373; BOS is prepended by the
         request manager when add_special_tokens is set).
@@ -372,7 +417,10 @@ class RequestManager:
         (:362-369): the prompt is that many copies of token 15 and `prompt` is
         ignored; it must be below max_sequence_length (the reference asserts).
         Deviation: max_new_tokens counts from that prompt here, where the
-        reference leaves max_length unset in this mode."""
+        reference leaves max_length unset in this mode.
+
+        lora_id: the adapter (Model.load_lora) the LLM applies to this
+        request, -1 for none; an id that is not loaded is rejected (0)."""
         if benchmarking_tokens >= 0:
             if benchmarking_tokens >= self.max_sequence_length:
                 raise ValueError("Benchmarking tokens exceed max sequence length")
@@ -384,8 +432,9 @@ class RequestManager:
                                  "'Tokenizer is null!'")
             prompt = self.tokenizer.encode(prompt)
         arr = F.int_array(list(prompt))
-        g = F.lib().ffmi_rm_register_request(self.handle, arr, len(prompt), max_length,
-                                             max_new_tokens, int(add_special_tokens))
+        g = F.lib().ffmi_rm_register_request_ex(self.handle, arr, len(prompt), max_length,
+                                                max_new_tokens, int(add_special_tokens),
+                                                int(lora_id))
         if g > 0:
             self.guids.append(g)
             self._add_special[g] = bool(add_special_tokens)
@@ -432,10 +481,12 @@ class RequestManager:
 
 
 def generate(rm: RequestManager, llm: Model, prompts, max_length=-1, max_new_tokens=-1,
-             spec: Optional[bool] = None):
-    """FFModel::generate (request_manager.cc:2880-2911): register, serve, collect."""
-    guids = [rm.register_new_request(p, max_length=max_length, max_new_tokens=max_new_tokens)
-             for p in prompts]
+             spec: Optional[bool] = None, lora_ids=None):
+    """FFModel::generate (request_manager.cc:2880-2911): register, serve, collect.
+    lora_ids: one adapter id per prompt (-1: none), or None."""
+    ids = list(lora_ids) if lora_ids is not None else [-1] * len(prompts)
+    guids = [rm.register_new_request(p, max_length=max_length, max_new_tokens=max_new_tokens,
+                                     lora_id=a) for p, a in zip(prompts, ids)]
     if spec is None:
         spec = llm.mode == "tree"
     if spec:

@@ -532,6 +532,66 @@ ffmi_status ffmi_model_create(const ffmi_llama_config *cfg, const ffmi_model_opt
 #define FFMI_MODEL_NATIVE_GQA 1u
 ffmi_status ffmi_model_create_ex(const ffmi_llama_config *cfg, const ffmi_model_opts *o,
                                  unsigned flags, ffmi_model **out);
+/*   FFMI_MODEL_LORA: the model serves LoRA adapters on down_proj (the
+ *   reference's LoraLinear on the MLP's down projection, lora_linear.cc),
+ *   one adapter per request at most, requests of different adapters and of
+ *   none in one batch.  fp16 INC and TREE models at tp_size 1 only: BEAM
+ *   (SSMs run without adapters), full_precision and tp_size > 1 return
+ *   FFMI_ERR_UNSUPPORTED ("lora" in ffmi_last_error).  In a step where some
+ *   row has an adapter, down_proj runs outside the fused residual norms, its
+ *   split-K sums are rounded to fp16 [T][H] and ffmi_lora_apply follows on
+ *   that (FFMI_DBG_DOWN then holds the adapted output); a step without
+ *   adapters is the step of a model without the flag, launch for launch. */
+/*   (bit value 4: 2 stays an unknown flag, FFMI_ERR_INVALID, as it was before
+ *   the adapters came and as callers written against that may rely on) */
+#define FFMI_MODEL_LORA 4u
+/* LoRA adapters of a FFMI_MODEL_LORA model.  Adapter ids are process-wide
+ * (0 .. FFMI_LORA_MAX_ADAPTERS - 1): a request names one at registration
+ * (ffmi_rm_register_request_ex) and the model that loaded it serves it.
+ *   load: A [L][rank][F] and B [L][H][rank] fp16 host arrays, row-major as
+ *   HF PEFT stores lora_A.weight / lora_B.weight of every layer's down_proj;
+ *   scaling = fp16(alpha / rank).  1 <= rank <= FFMI_LORA_MAX_RANK (stored
+ *   zero-padded); a larger rank: FFMI_ERR_UNSUPPORTED ("lora").  No free id:
+ *   FFMI_ERR_OOM.  Device storage is allocated here, never in a step.
+ *   load_folder: the reference's per-tensor files
+ *   layers.{i}.mlp.down_proj.lora_A.weight / .lora_B.weight in `folder`
+ *   (peft_weight_allocator.cc:171-240), fp16 or fp32 by file size.  A file of
+ *   another target module in the folder (q_proj, up_proj, ...):
+ *   FFMI_ERR_UNSUPPORTED ("lora").
+ *   unload: FFMI_ERR_INVALID while a registered, unfinished request names the
+ *   adapter, or for an id this model did not load. */
+#define FFMI_LORA_MAX_ADAPTERS 8
+#define FFMI_LORA_MAX_RANK 64
+ffmi_status ffmi_model_lora_load(ffmi_model *m, int rank, float alpha, const void *A,
+                                 const void *B, int *id_out);
+ffmi_status ffmi_model_lora_load_folder(ffmi_model *m, const char *folder, int rank, float alpha,
+                                        int *id_out);
+ffmi_status ffmi_model_lora_unload(ffmi_model *m, int id);
+/* The LoRA update of a [T][H] fp16 projection output, in place:
+ *   h[t][j]  = fp16(sum_k x[t][k] A[j][k])            (fp32 accumulation)
+ *   y[t][n]  = fp16(float(y[t][n]) + scale * sum_j h[t][j] B[n][j])
+ * for every row t with 0 <= slots[t] < FFMI_LORA_MAX_ADAPTERS and a non-NULL
+ * table entry; other rows of y are not written.  A row's result depends on
+ * the row, its adapter and F only (F is split in 256-column parts whose fp32
+ * partial sums are added in part order), not on T or the rows around it.
+ *   x: [T][F] fp16 row-major, or packed activation tiles (x_packed != 0;
+ *   ffmi_pack_activations).  slots: [T] int32 on the device.  table:
+ *   FFMI_LORA_MAX_ADAPTERS device-resident ffmi_lora_entry; A packed as
+ *   ffmi_pack_activations packs a [64][F] matrix (rows >= rank zero), B
+ *   [H][64] row-major (columns >= rank zero), scale = float(fp16(alpha / r)).
+ *   ws: ffmi_lora_workspace_bytes(T, F) bytes of device scratch.
+ *   h_out: NULL, or [T][64] fp16 (rows with an adapter are written: the
+ *   kernel's own h, zero beyond the adapter's rank rounded up to 16).
+ * FFMI_ERR_INVALID: F % 32, H % 8, a missing or short workspace. */
+typedef struct {
+  const void *A, *B;
+  float scale;
+  int rank;
+} ffmi_lora_entry;
+size_t ffmi_lora_workspace_bytes(int T, int F);
+ffmi_status ffmi_lora_apply(const void *x, int T, int F, int H, const int32_t *slots,
+                            const ffmi_lora_entry *table, void *y, int x_packed, void *ws,
+                            size_t ws_bytes, void *h_out, ffmi_stream stream);
 /* bytes of the K plus V caches of all layers (this rank's; fp16 models) */
 size_t ffmi_model_kv_cache_bytes(ffmi_model *m);
 void ffmi_model_destroy(ffmi_model *m);
@@ -706,6 +766,13 @@ ffmi_status ffmi_rm_set_old_llama_tokenizer(ffmi_rm *rm, int enable);
 int64_t ffmi_rm_register_request(ffmi_rm *rm, const int *prompt, int n_prompt,
                                  int max_length, int max_new_tokens,
                                  int add_special_tokens);
+/* The same with a LoRA adapter: lora_id -1 (none; ffmi_rm_register_request)
+ * or the id of a loaded adapter (ffmi_model_lora_load), which every LLM step
+ * of the request applies; SSM steps run without it.  An id that is not loaded
+ * returns 0. */
+int64_t ffmi_rm_register_request_ex(ffmi_rm *rm, const int *prompt, int n_prompt,
+                                    int max_length, int max_new_tokens,
+                                    int add_special_tokens, int lora_id);
 /* Run the serve loop until every registered request completes
  * (serve_incr_decoding / serve_spec_infer, request_manager.cc:3012-3173). */
 ffmi_status ffmi_rm_serve_incr_decoding(ffmi_rm *rm, ffmi_model *llm);
@@ -875,7 +942,9 @@ const char *ffmi_last_error(void);
  * ffmi_debug_allreduce_partials, ffmi_debug_rmsnorm_gather; and of the
  * output projection folded into the fused attention: ffmi_debug_attn_oproj;
  * and per-token log-probabilities: ffmi_token_logprobs(_workspace_bytes),
- * ffmi_model_set_logprobs, ffmi_rm_get_logprobs */
+ * ffmi_model_set_logprobs, ffmi_rm_get_logprobs; and LoRA adapters on
+ * down_proj: FFMI_MODEL_LORA, ffmi_model_lora_load(_folder) / _unload,
+ * ffmi_lora_apply(_workspace_bytes), ffmi_rm_register_request_ex */
 const char *ffmi_version(void);
 
 #ifdef __cplusplus
