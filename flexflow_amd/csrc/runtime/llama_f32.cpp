@@ -16,12 +16,16 @@
 
 #include <algorithm>
 #include <cmath>
-#include <map>
 #include <string>
 #include <tuple>
 #include <vector>
 
+#include "graph_cache.h"
 #include "model.h"
+
+// return a failed status to the caller
+#define TRY(x) \
+  do { const ffmi_status st_ = (x); if (st_ != FFMI_OK) return st_; } while (0)
 
 namespace ffmi {
 
@@ -50,13 +54,13 @@ struct LlamaF32 : public ffmi_model {
   ffmi_batch_dev *batch = nullptr;
   PackedStep ps;
   std::vector<void *> allocs;
-  std::map<std::tuple<int, int, int, int, size_t>, hipGraphExec_t> graphs;
+  GraphCache<std::tuple<int, int, int, int, size_t>> graphs{256};
   bool use_graphs = getenv("FFMI_NO_GRAPHS") == nullptr;
   int dbg = 0, dbg_T = -1;
 
   ~LlamaF32() override {
     if (stream) (void)hipStreamSynchronize(stream);
-    for (auto &kv : graphs) (void)hipGraphExecDestroy(kv.second);
+    graphs.clear();
     for (auto &L : layers) ffmi_attn_destroy(L.attn);
     for (void *p : allocs) (void)hipFree(p);
     if (res_h) (void)hipHostFree(res_h);
@@ -89,48 +93,14 @@ struct LlamaF32 : public ffmi_model {
     return FFMI_OK;
   }
 
-  // One tensor of a reference-format checkpoint (file_loader.cc:363-389), fp32
-  // or fp16 files (full precision loads the fp32 files; half files widen
-  // exactly), GQA K/V replicated per query head (:292-302)
+  // One tensor of a reference-format checkpoint (tensor_file.h): full
+  // precision loads the fp32 files, half files widen exactly; GQA K/V
+  // replicated per query head
   ffmi_status load_tensor(std::vector<float> &out, size_t n, const std::string &hf_name) {
-    std::string file = hf_name.rfind("model.", 0) == 0 ? hf_name.substr(6) : hf_name;
-    const bool kv = file.find("self_attn.k_proj") != std::string::npos ||
-                    file.find("self_attn.v_proj") != std::string::npos;
-    const int group = kv ? c.num_heads / c.num_kv_heads : 1;
-    const size_t n_file = n / group;
-    const std::string path = weights_folder + "/" + file;
-    FILE *f = fopen(path.c_str(), "rb");
-    if (!f) {
-      ffmi_set_last_error(("weight file not found: " + path).c_str(), __FILE__, __LINE__);
-      return FFMI_ERR_INVALID;
-    }
-    fseek(f, 0, SEEK_END);
-    const long bytes = ftell(f);
-    fseek(f, 0, SEEK_SET);
-    std::vector<float> v(n_file);
-    bool ok = false;
-    if (bytes == (long)(n_file * 4)) {
-      ok = fread(v.data(), 4, n_file, f) == n_file;
-    } else if (bytes == (long)(n_file * 2)) {
-      std::vector<_Float16> h16(n_file);
-      ok = fread(h16.data(), 2, n_file, f) == n_file;
-      for (size_t i = 0; ok && i < n_file; ++i) v[i] = (float)h16[i];
-    }
-    fclose(f);
-    if (!ok) {
-      ffmi_set_last_error(("weight file has the wrong size: " + path).c_str(), __FILE__, __LINE__);
-      return FFMI_ERR_INVALID;
-    }
-    out.resize(n);
-    const size_t row_block = n_file / c.num_kv_heads;
-    if (group > 1) {
-      for (int i = 0; i < c.num_heads; ++i)
-        memcpy(out.data() + (size_t)i * row_block, v.data() + (size_t)(i / group) * row_block,
-               row_block * 4);
-    } else {
-      memcpy(out.data(), v.data(), n * 4);
-    }
-    return FFMI_OK;
+    std::string path;
+    return tensor_status(read_checkpoint_tensor(weights_folder, hf_name, n, c.num_heads,
+                                                c.num_kv_heads, &out, &path),
+                         "weight file", path);
   }
 
   // the full [rows][cols] tensor into tmp: seeded synthetic (orc_gen_weight
@@ -186,9 +156,6 @@ struct LlamaF32 : public ffmi_model {
     const int tree = mode == FFMI_MODEL_INC ? 0 : o.max_tree_tokens;
     slots = (o.max_seq_len + tree + 31) & ~31;  // ffmi_attn_create's slot count
     FFMI_CHECK((size_t)(d + 256 + slots) * 4 <= 64 * 1024, FFMI_ERR_UNSUPPORTED);
-    ffmi_status st;
-#define TRY(x) \
-  do { if ((st = (x)) != FFMI_OK) return st; } while (0)
     TRY(ffmi_batch_create(Tm, o.max_requests, &batch));
     TRY(alloc(&res, (size_t)Tm * H));
     TRY(alloc(&h, (size_t)Tm * H));
@@ -280,7 +247,6 @@ struct LlamaF32 : public ffmi_model {
         allocs.erase(it);
         break;
       }
-#undef TRY
     return FFMI_OK;
   }
 
@@ -293,9 +259,6 @@ struct LlamaF32 : public ffmi_model {
   ffmi_status enqueue(int k, size_t blob_bytes, bool record_upload) {
     const int T = (int)ps.tokens.size();
     const float eps = c.rms_eps;
-    ffmi_status st;
-#define TRY(x) \
-  do { if ((st = (x)) != FFMI_OK) return st; } while (0)
     TRY(batch_copy(batch, blob_bytes, stream, record_upload));
     const char *blob = batch->dev;
     for (int l = 0; l < c.num_layers; ++l) {
@@ -321,7 +284,6 @@ struct LlamaF32 : public ffmi_model {
     float *probs_d = reinterpret_cast<float *>(res_d + (size_t)T * k);
     FFMI_HIP(launch_softmax_topk_f32(logits, T, V, k, res_d, probs_d, stream));
     FFMI_HIP(hipMemcpyAsync(res_h, res_d, (size_t)T * k * 8, hipMemcpyDeviceToHost, stream));
-#undef TRY
     return FFMI_OK;
   }
 
@@ -341,28 +303,13 @@ struct LlamaF32 : public ffmi_model {
     const bool graph = use_graphs && !dbg && P == 1;
     if (graph) {
       const auto key = std::make_tuple(T, batch->num_work, batch->num_commits, k, bytes);
-      auto it = graphs.find(key);
-      if (it == graphs.end()) {
-        if (graphs.size() >= 256) {
-          for (auto &kv : graphs) (void)hipGraphExecDestroy(kv.second);
-          graphs.clear();
-        }
-        hipGraph_t g = nullptr;
-        FFMI_HIP(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-        st = enqueue(k, bytes, false);
-        const hipError_t ce = hipStreamEndCapture(stream, &g);
-        if (st != FFMI_OK || ce != hipSuccess) {
-          if (g) (void)hipGraphDestroy(g);
-          if (st != FFMI_OK) return st;
-          FFMI_HIP(ce);
-        }
-        hipGraphExec_t ex = nullptr;
-        const hipError_t ie = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(g);
-        FFMI_HIP(ie);
-        it = graphs.emplace(key, ex).first;
+      hipGraphExec_t ex = graphs.find(key);
+      if (!ex) {
+        if (graphs.full()) graphs.clear();
+        TRY(capture_graph(stream, [&] { return enqueue(k, bytes, false); }, &ex));
+        graphs.insert(key, ex);
       }
-      FFMI_HIP(hipGraphLaunch(it->second, stream));
+      FFMI_HIP(hipGraphLaunch(ex, stream));
     } else {
       st = enqueue(k, bytes, true);
       if (st != FFMI_OK) return st;

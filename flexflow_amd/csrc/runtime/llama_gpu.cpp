@@ -19,13 +19,18 @@
 #include <algorithm>
 #include <cmath>
 
-#include <string>
 #include <map>
+#include <string>
 #include <tuple>
 #include <vector>
 
+#include "graph_cache.h"
 #include "model.h"
 #include "request_manager.h"  // (now_us)
+
+// return a failed status to the caller
+#define TRY(x) \
+  do { const ffmi_status st_ = (x); if (st_ != FFMI_OK) return st_; } while (0)
 
 namespace ffmi {
 
@@ -37,6 +42,24 @@ struct Layer {
   ffmi_attn *attn = nullptr;
 };
 
+// One step as enqueue sees it: the staging batch and result slot it runs on
+// (slot 0 unless a chained beam step), its rows, results per row, and the
+// bytes of its staged blob.  Built on the stack by whoever launches the step.
+struct Step {
+  ffmi_batch_dev *batch;
+  int slot, T, k;
+  size_t blob_bytes;
+};
+
+// A per-row side array of a step (4-byte elements): filled from the batch the
+// scheduler built, appended to the step's staged blob at `off` (stage_extra)
+template <typename E>
+struct StepExtra {
+  static_assert(sizeof(E) == 4, "4-byte elements");
+  std::vector<E> v;
+  size_t off = 0;
+};
+
 struct LlamaGPU : public ffmi_model {
   ffmi_llama_config c{};
   ffmi_model_opts o{};
@@ -44,6 +67,7 @@ struct LlamaGPU : public ffmi_model {
   bool uses_collectives() const override { return o.tp_size > 1; }
   std::string weights_folder;  // reference-format checkpoint ("" = synthetic)
   int Hl = 0, Fl = 0, d = 0, heads_l = 0, slots = 0;
+  int Tm = 0;  // max_tokens in whole 16-row groups (packed tiles cover them)
   // FFMI_MODEL_NATIVE_GQA with num_kv_heads < num_heads: this rank's K/V heads,
   // their width and the qkv row [Hl | Hkv | Hkv]; otherwise K/V are (or are
   // replicated to) heads_l heads: kvh_l = heads_l, Hkv = Hl, Nqkv = 3 Hl
@@ -70,7 +94,7 @@ struct LlamaGPU : public ffmi_model {
   // top-p sampling (ffmi_model_set_sampling; llama.cc:286-289) instead of the
   // greedy tail.  The host draws one uniform per row, u = (ffmi_sampling_
   // counter(seed, request guid, position of the token produced) + 1) * 2^-24,
-  // and appends them to the step's blob behind its records (step_u_off), so
+  // and appends them to the step's blob behind its records (step_u.off), so
   // they ride the step's one upload and a graph replay reads fresh values
   bool sampling = false;
   float temperature = 0.8f, topp = 0.6f;
@@ -80,23 +104,18 @@ struct LlamaGPU : public ffmi_model {
   // allocated when sampling is first turned on
   uint16_t *sample_ws = nullptr;
   size_t sample_ws_bytes = 0;
-  std::vector<float> step_u;
-  size_t step_u_off = 0;
+  StepExtra<float> step_u;
   ffmi_status set_sampling(bool on, float temp, float p, uint64_t seed) override {
     const char *why = mode != FFMI_MODEL_INC
                           ? "sampling: a BEAM / TREE model decodes greedily (a sampled pick "
                             "cannot verify a greedy token tree)"
                           : Vl != c.vocab_size && !o.comm ? "sampling: vocab-sharded lm_head"
                                                           : nullptr;
-    if (why) {
-      ffmi_set_last_error(why, __FILE__, __LINE__);
-      return FFMI_ERR_UNSUPPORTED;
-    }
-    const size_t Tm = (size_t)((o.max_tokens + 15) & ~15);
+    if (why) return refuse(why);
     if (on && !sample_ws) {
       sample_ws_bytes = Vl != c.vocab_size ? ffmi_vocab_shard_sample_scratch_bytes(
-                                                 ffmi::comm_size(o.comm), (int)Tm, Vl)
-                                           : ffmi::sample_topp_workspace_bytes((int)Tm, Vl);
+                                                 ffmi::comm_size(o.comm), Tm, Vl)
+                                           : ffmi::sample_topp_workspace_bytes(Tm, Vl);
       const ffmi_status st = alloc(&sample_ws, (sample_ws_bytes + 1) / 2);
       if (st != FFMI_OK) return st;
     }
@@ -109,22 +128,13 @@ struct LlamaGPU : public ffmi_model {
   }
   // the step's draws, from the batch the scheduler built
   void draw_step_u(const BatchConfig &bc) {
-    step_u.resize(bc.num_tokens);
+    step_u.v.resize(bc.num_tokens);
     for (int t = 0; t < bc.num_tokens; ++t) {
       const auto &ti = bc.tokensInfo[t];
       const uint32_t ctr = ffmi_sampling_counter(
           sampling_seed, bc.requestsInfo[ti.request_index].request_guid, ti.abs_depth_in_request + 1);
-      step_u[t] = (float)(ctr + 1u) * (1.0f / 16777216.0f);
+      step_u.v[t] = (float)(ctr + 1u) * (1.0f / 16777216.0f);
     }
-  }
-  // append them to the staged blob (forward_launch, after batch_stage)
-  ffmi_status stage_step_u(int T, size_t *bytes) {
-    step_u_off = *bytes;
-    const size_t n = ((size_t)T * sizeof(float) + 15) & ~(size_t)15;
-    FFMI_CHECK((int)step_u.size() == T && *bytes + n <= batch->cap, FFMI_ERR_INVALID);
-    memcpy(batch->host + *bytes, step_u.data(), (size_t)T * sizeof(float));
-    *bytes += n;
-    return FFMI_OK;
   }
   // per-token log-probabilities (ffmi_model_set_logprobs): ffmi_token_logprobs
   // behind the pick, in the same stream and captured graph.  The rows' targets
@@ -140,18 +150,13 @@ struct LlamaGPU : public ffmi_model {
   int32_t *lp_picks = nullptr;  // [Tm]
   char *lp_ws = nullptr;
   size_t lp_ws_bytes = 0;
-  std::vector<int32_t> step_targets;
-  size_t step_targets_off = 0;
+  StepExtra<int32_t> step_targets;
   bool logprobs_on() const override { return logprobs; }
   ffmi_status set_logprobs(bool on) override {
     const char *why = mode == FFMI_MODEL_BEAM
                           ? "logprobs: a BEAM model's picks are proposals, not tokens"
                           : Vl != c.vocab_size ? "logprobs: vocab-sharded lm_head" : nullptr;
-    if (why) {
-      ffmi_set_last_error(why, __FILE__, __LINE__);
-      return FFMI_ERR_UNSUPPORTED;
-    }
-    const size_t Tm = (size_t)((o.max_tokens + 15) & ~15);
+    if (why) return refuse(why);
     if (on && !lp_ws) {
       FFMI_CHECK(Vl <= ffmi::sample_topp_max_v(), FFMI_ERR_UNSUPPORTED);
       if (!lp_h)
@@ -159,7 +164,7 @@ struct LlamaGPU : public ffmi_model {
                                hipHostMallocCoherent | hipHostMallocMapped));
       ffmi_status st = lp_picks ? FFMI_OK : alloc(&lp_picks, Tm);
       if (st != FFMI_OK) return st;
-      lp_ws_bytes = ffmi::token_logprobs_workspace_bytes((int)Tm, Vl);
+      lp_ws_bytes = ffmi::token_logprobs_workspace_bytes(Tm, Vl);
       if ((st = alloc(&lp_ws, lp_ws_bytes)) != FFMI_OK) return st;
     }
     // (the captured graphs hold the step with or without the launches)
@@ -168,19 +173,10 @@ struct LlamaGPU : public ffmi_model {
     logprobs = on;
     return FFMI_OK;
   }
-  // the step's targets, from the batch the scheduler built, appended to the
-  // staged blob (forward_launch, behind the draws)
+  // the step's targets, from the batch the scheduler built
   void take_step_targets(const BatchConfig &bc) {
-    step_targets.resize(bc.num_tokens);
-    for (int t = 0; t < bc.num_tokens; ++t) step_targets[t] = bc.tokensInfo[t].score_id;
-  }
-  ffmi_status stage_step_targets(int T, size_t *bytes) {
-    step_targets_off = *bytes;
-    const size_t n = ((size_t)T * sizeof(int32_t) + 15) & ~(size_t)15;
-    FFMI_CHECK((int)step_targets.size() == T && *bytes + n <= batch->cap, FFMI_ERR_INVALID);
-    memcpy(batch->host + *bytes, step_targets.data(), (size_t)T * sizeof(int32_t));
-    *bytes += n;
-    return FFMI_OK;
+    step_targets.v.resize(bc.num_tokens);
+    for (int t = 0; t < bc.num_tokens; ++t) step_targets.v[t] = bc.tokensInfo[t].score_id;
   }
   // LoRA adapters on down_proj (FFMI_MODEL_LORA; lora_linear.cc): under the
   // flag the down projection runs with its own reduce pass, outside the fused
@@ -196,34 +192,25 @@ struct LlamaGPU : public ffmi_model {
   std::vector<ffmi_lora_entry> lora_tab_h;
   uint16_t *lora_A[FFMI_LORA_MAX_ADAPTERS] = {}, *lora_B[FFMI_LORA_MAX_ADAPTERS] = {};
   float *lora_ws = nullptr;
-  std::vector<int32_t> step_slots;
-  size_t step_slots_off = 0;
+  StepExtra<int32_t> step_slots;
   bool step_lora_any = false;
   void take_step_slots(const BatchConfig &bc) {
-    step_slots.resize(bc.num_tokens);
+    step_slots.v.resize(bc.num_tokens);
     step_lora_any = false;
     for (int t = 0; t < bc.num_tokens; ++t) {
       const int a = bc.requestsInfo[bc.tokensInfo[t].request_index].lora_id;
-      step_slots[t] = a >= 0 && a < FFMI_LORA_MAX_ADAPTERS && lora_A[a] ? a : -1;
-      step_lora_any = step_lora_any || step_slots[t] >= 0;
+      step_slots.v[t] = a >= 0 && a < FFMI_LORA_MAX_ADAPTERS && lora_A[a] ? a : -1;
+      step_lora_any = step_lora_any || step_slots.v[t] >= 0;
     }
   }
-  ffmi_status stage_step_slots(int T, size_t *bytes) {
-    step_slots_off = *bytes;
-    const size_t n = ((size_t)T * sizeof(int32_t) + 15) & ~(size_t)15;
-    FFMI_CHECK((int)step_slots.size() == T && *bytes + n <= batch->cap, FFMI_ERR_INVALID);
-    memcpy(batch->host + *bytes, step_slots.data(), (size_t)T * sizeof(int32_t));
-    *bytes += n;
-    return FFMI_OK;
-  }
-  ffmi_status lora_refuse(const char *why) {
+  static ffmi_status refuse(const char *why) {
     ffmi_set_last_error(why, __FILE__, __LINE__);
     return FFMI_ERR_UNSUPPORTED;
   }
   ffmi_status lora_load(int rank, float alpha, const void *A, const void *B, int *id_out) override {
     if (!lora) return ffmi_model::lora_load(rank, alpha, A, B, id_out);
     FFMI_CHECK(A && B && id_out && rank >= 1 && std::isfinite(alpha), FFMI_ERR_INVALID);
-    if (rank > FFMI_LORA_MAX_RANK) return lora_refuse("lora: rank above FFMI_LORA_MAX_RANK");
+    if (rank > FFMI_LORA_MAX_RANK) return refuse("lora: rank above FFMI_LORA_MAX_RANK");
     const int L = c.num_layers, F = Fl, H = c.hidden, R = FFMI_LORA_MAX_RANK;
     // A as the packed activation tiles of a [R][F] matrix (one MFMA operand
     // fragment per 16 ranks x 32 columns), B [H][R]; zero beyond the rank
@@ -272,40 +259,14 @@ struct LlamaGPU : public ffmi_model {
     *id_out = id;
     return FFMI_OK;
   }
-  // one per-tensor file of the reference's adapter folder (fp16, or fp32
-  // converted round to nearest even, by file size as load_tensor)
+  // one per-tensor file of the reference's adapter folder
   ffmi_status lora_read(const std::string &path, size_t n, uint16_t *dst) {
-    FILE *f = fopen(path.c_str(), "rb");
-    if (!f) {
-      ffmi_set_last_error(("lora: adapter file not found: " + path).c_str(), __FILE__, __LINE__);
-      return FFMI_ERR_INVALID;
-    }
-    fseek(f, 0, SEEK_END);
-    const long bytes = ftell(f);
-    fseek(f, 0, SEEK_SET);
-    bool ok = false;
-    if (bytes == (long)(n * 2)) {
-      ok = fread(dst, 2, n, f) == n;
-    } else if (bytes == (long)(n * 4)) {
-      std::vector<float> h32(n);
-      ok = fread(h32.data(), 4, n, f) == n;
-      for (size_t i = 0; ok && i < n; ++i) {
-        const _Float16 v = (_Float16)h32[i];
-        memcpy(&dst[i], &v, 2);
-      }
-    }
-    fclose(f);
-    if (!ok) {
-      ffmi_set_last_error(("lora: adapter file has the wrong size: " + path).c_str(), __FILE__,
-                          __LINE__);
-      return FFMI_ERR_INVALID;
-    }
-    return FFMI_OK;
+    return tensor_status(read_tensor(path, n, dst), "lora: adapter file", path);
   }
   ffmi_status lora_load_folder(const char *folder, int rank, float alpha, int *id_out) override {
     if (!lora) return ffmi_model::lora_load_folder(folder, rank, alpha, id_out);
     FFMI_CHECK(rank >= 1, FFMI_ERR_INVALID);
-    if (rank > FFMI_LORA_MAX_RANK) return lora_refuse("lora: rank above FFMI_LORA_MAX_RANK");
+    if (rank > FFMI_LORA_MAX_RANK) return refuse("lora: rank above FFMI_LORA_MAX_RANK");
     // only down_proj is served: an adapter tensor of any other module refuses
     if (DIR *dir = opendir(folder)) {
       bool other = false;
@@ -315,7 +276,7 @@ struct LlamaGPU : public ffmi_model {
           other = true;
       }
       closedir(dir);
-      if (other) return lora_refuse("lora: the adapter targets a module other than down_proj");
+      if (other) return refuse("lora: the adapter targets a module other than down_proj");
     }
     const int L = c.num_layers, F = c.intermediate, H = c.hidden;
     std::vector<uint16_t> a((size_t)L * rank * F), b((size_t)L * H * rank);
@@ -398,11 +359,12 @@ struct LlamaGPU : public ffmi_model {
   int32_t *ids_h = nullptr;  // [kChain slots][Tm * 4 ids | Tm * 4 probs], pinned
   // chained beam steps (beam_launch_chained): one staging blob and one result
   // slot per step of a speculation phase; the top-k also leaves each slot's
-  // ids in device memory (ids_dev) for the next step's embedding gather
+  // ids in device memory (ids_dev) for the next step's embedding gather.
+  // Slot 0 is also every unchained step's; the others exist only in a BEAM
+  // model at TP = 1 (init), the only one that chains (can_chain_beam)
   static constexpr int kChain = BeamSearchBatchConfig::MAX_BEAM_DEPTH;
   ffmi_batch_dev *chain_batch[kChain] = {};
   int32_t *ids_dev = nullptr;  // [kChain][Tm * 4]
-  int cur_slot = 0;
   size_t slot_results[kChain] = {};  // [T][k] ids of each slot
   std::vector<int> slot_map[kChain];  // scheduler entry -> [T][k] index (beam_result_layout)
   hipEvent_t slot_ev[kChain] = {};     // recorded behind each launched slot
@@ -410,10 +372,10 @@ struct LlamaGPU : public ffmi_model {
   bool slot_ev_live[kChain] = {};      // slot_ev recorded for the chain in flight
   int last_slot = -1;                  // highest slot launched since the last wait
   bool chain_ok = !getenv("FFMI_SSM_CHAIN") || atoi(getenv("FFMI_SSM_CHAIN")) != 0;
-  size_t slot_ints() const { return (size_t)((o.max_tokens + 15) & ~15) * 4 * 2; }
+  size_t slot_ints() const { return (size_t)Tm * 4 * 2; }
+  int32_t *slot_ids_h(int slot) const { return ids_h + slot * slot_ints(); }
+  int32_t *slot_ids_dev(int slot) const { return ids_dev + (size_t)slot * (slot_ints() / 2); }
   bool result_copy = getenv("FFMI_RESULT_COPY") && atoi(getenv("FFMI_RESULT_COPY")) != 0;
-  float *probs_h = nullptr;
-  ffmi_batch_dev *batch = nullptr;
   PackedStep ps;
   std::vector<void *> allocs;
 
@@ -557,13 +519,13 @@ struct LlamaGPU : public ffmi_model {
     return k == FFMI_DBG_ATTN_NORM || k == FFMI_DBG_FFN_NORM || k == FFMI_DBG_ATTN_OUT ||
            k == FFMI_DBG_MLP_ACT || (k == FFMI_DBG_HIDDEN && layer == c.num_layers);
   }
-  size_t dbg_tm() const { return (size_t)((o.max_tokens + 15) & ~15); }
+  static int rows16(int T) { return (T + 15) / 16 * 16; }  // rows of T's packed tiles
   ffmi_status set_debug(int enable) override {
     if (enable && !dbg_buf) {
       size_t total = 0;
       for (int k = 0; k < kDbgKinds; ++k) {
         dbg_off[k] = total;
-        total += (size_t)dbg_layers(k) * dbg_tm() * std::max(0L, debug_width(k));
+        total += (size_t)dbg_layers(k) * Tm * std::max(0L, debug_width(k));
       }
       if (alloc(&dbg_buf, total) != FFMI_OK) return FFMI_ERR_OOM;
     }
@@ -572,11 +534,11 @@ struct LlamaGPU : public ffmi_model {
     return FFMI_OK;
   }
   uint16_t *dbg_slot(int k, int l) const {
-    return dbg_buf + dbg_off[k] + (size_t)l * dbg_tm() * debug_width(k);
+    return dbg_buf + dbg_off[k] + (size_t)l * Tm * debug_width(k);
   }
   // capture src ([T][width], or packed tiles covering whole 16-row groups)
   ffmi_status dbg_copy(int k, int l, const uint16_t *src, int T) {
-    const size_t rows = dbg_is_packed(k, l) ? (size_t)((T + 15) & ~15) : (size_t)T;
+    const size_t rows = (size_t)(dbg_is_packed(k, l) ? rows16(T) : T);
     FFMI_HIP(hipMemcpyAsync(dbg_slot(k, l), src, rows * debug_width(k) * 2,
                             hipMemcpyDeviceToDevice, stream));
     return FFMI_OK;
@@ -598,7 +560,7 @@ struct LlamaGPU : public ffmi_model {
     if (cap < (long)T * width) return -1;
     const uint16_t *src = which == FFMI_DBG_LOGITS ? logits : dbg_slot(which, layer);
     const bool pk = which != FFMI_DBG_LOGITS && dbg_is_packed(which, layer);
-    const size_t n = (size_t)(pk ? (T + 15) & ~15 : T) * width;
+    const size_t n = (size_t)(pk ? rows16(T) : T) * width;
     std::vector<uint16_t> raw(n);
     if (hipMemcpy(raw.data(), src, n * 2, hipMemcpyDeviceToHost) != hipSuccess) return -1;
     for (int t = 0; t < T; ++t)
@@ -729,8 +691,7 @@ struct LlamaGPU : public ffmi_model {
     for (void *p : allocs) (void)hipFree(p);
     if (ids_h) (void)hipHostFree(ids_h);
     if (lp_h) (void)hipHostFree(lp_h);
-    for (int i = 1; i < kChain; ++i) ffmi_batch_destroy(chain_batch[i]);
-    ffmi_batch_destroy(batch);
+    for (ffmi_batch_dev *b : chain_batch) ffmi_batch_destroy(b);
     if (stream) (void)hipStreamDestroy(stream);
   }
 
@@ -744,51 +705,14 @@ struct LlamaGPU : public ffmi_model {
     return FFMI_OK;
   }
 
-  // One tensor of a reference-format checkpoint (file_loader.cc:363-389
-  // load_from_file; names as convert_hf_model writes them): the HF name
-  // without "model.", raw fp16 or fp32 (converted, round to nearest even).
-  // k/v projections of a GQA checkpoint hold num_kv_heads * d rows; row
-  // block of query head i = kv head i / (heads / kv_heads) (:292-302).
+  // One tensor of a reference-format checkpoint (tensor_file.h); a GQA
+  // checkpoint's K/V replicated per query head unless native_gqa keeps them
   ffmi_status load_tensor(uint16_t *dst, size_t n, const std::string &hf_name) {
-    std::string file = hf_name.rfind("model.", 0) == 0 ? hf_name.substr(6) : hf_name;
-    const bool kv = file.find("self_attn.k_proj") != std::string::npos ||
-                    file.find("self_attn.v_proj") != std::string::npos;
-    const int group = kv && !native_gqa ? c.num_heads / c.num_kv_heads : 1;  // (native: as stored)
-    const size_t n_file = n / group;
-    const std::string path = weights_folder + "/" + file;
-    FILE *f = fopen(path.c_str(), "rb");
-    if (!f) {
-      ffmi_set_last_error(("weight file not found: " + path).c_str(), __FILE__, __LINE__);
-      return FFMI_ERR_INVALID;
-    }
-    fseek(f, 0, SEEK_END);
-    const long bytes = ftell(f);
-    fseek(f, 0, SEEK_SET);
-    std::vector<uint16_t> h16(n_file);
-    bool ok = false;
-    if (bytes == (long)(n_file * 2)) {
-      ok = fread(h16.data(), 2, n_file, f) == n_file;
-    } else if (bytes == (long)(n_file * 4)) {
-      std::vector<float> h32(n_file);
-      ok = fread(h32.data(), 4, n_file, f) == n_file;
-      for (size_t i = 0; ok && i < n_file; ++i) {
-        const _Float16 v = (_Float16)h32[i];
-        memcpy(&h16[i], &v, 2);
-      }
-    }
-    fclose(f);
-    if (!ok) {
-      ffmi_set_last_error(("weight file has the wrong size: " + path).c_str(), __FILE__, __LINE__);
-      return FFMI_ERR_INVALID;
-    }
-    if (group > 1) {  // [kv_heads * d][H] -> [heads * d][H]
-      const size_t row_block = n_file / c.num_kv_heads;  // d rows of one head
-      std::vector<uint16_t> rep(n);
-      for (int i = 0; i < c.num_heads; ++i)
-        memcpy(rep.data() + (size_t)i * row_block, h16.data() + (size_t)(i / group) * row_block,
-               row_block * 2);
-      h16.swap(rep);
-    }
+    std::vector<uint16_t> h16;
+    std::string path;
+    const TensorRead r = read_checkpoint_tensor(weights_folder, hf_name, n, c.num_heads,
+                                                native_gqa ? c.num_heads : c.num_kv_heads, &h16, &path);
+    if (r != TensorRead::ok) return tensor_status(r, "weight file", path);
     FFMI_HIP(hipMemcpy(dst, h16.data(), n * 2, hipMemcpyHostToDevice));
     return FFMI_OK;
   }
@@ -825,7 +749,7 @@ struct LlamaGPU : public ffmi_model {
     Fl = F / P;
     FFMI_CHECK(H % 32 == 0 && Hl % 32 == 0 && Fl % 32 == 0, FFMI_ERR_UNSUPPORTED);
     FFMI_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-    const int Tm = (o.max_tokens + 15) & ~15;  // packed tiles cover 16-row groups
+    Tm = (o.max_tokens + 15) & ~15;
     packed = H % 32 == 0 && Hl % 32 == 0 && Fl % 32 == 0;
     {
       const double wbytes = 2.0 * c.num_layers * (((double)Nqkv + Hl) * H + 3.0 * Fl * H) +
@@ -834,10 +758,7 @@ struct LlamaGPU : public ffmi_model {
       if (const char *e = getenv("FFMI_W_STREAM"))  // A/B override: 0 / 1
         wstream = atoi(e) ? FFMI_W_STREAM : 0;
     }
-    ffmi_status st;
-#define TRY(x) \
-  do { if ((st = (x)) != FFMI_OK) return st; } while (0)
-    TRY(ffmi_batch_create(Tm, o.max_requests, &batch));
+    TRY(ffmi_batch_create(Tm, o.max_requests, &chain_batch[0]));
     TRY(alloc(&res, (size_t)Tm * H));
     TRY(alloc(&h, (size_t)Tm * H));
     TRY(alloc(&qkv, (size_t)Tm * Nqkv));
@@ -922,7 +843,6 @@ struct LlamaGPU : public ffmi_model {
     FFMI_HIP(hipHostMalloc((void **)&ids_h, (size_t)kChain * Tm * 4 * 2 * sizeof(int32_t),
                            hipHostMallocCoherent | hipHostMallocMapped));
     if (mode == FFMI_MODEL_BEAM) TRY(alloc(&ids_dev, (size_t)kChain * Tm * 4));
-    chain_batch[0] = batch;
     // the chained beam steps' staging batches, created here rather than on a
     // chain's first use: creating one clears its device blob on the legacy
     // stream, which fails -- and invalidates the capture -- while another
@@ -930,7 +850,7 @@ struct LlamaGPU : public ffmi_model {
     // process, ffmi_comm_create_local, beside their SSMs)
     if (mode == FFMI_MODEL_BEAM && o.tp_size == 1)
       for (int i = 1; i < kChain; ++i)
-        TRY(ffmi_batch_create((o.max_tokens + 15) & ~15, o.max_requests, &chain_batch[i]));
+        TRY(ffmi_batch_create(Tm, o.max_requests, &chain_batch[i]));
     // weights (seeded synthetic, orc_gen_weight spec), packed for MFMA
     uint16_t *tmp = nullptr;
     size_t tmp_elems = std::max((size_t)V * H, std::max((size_t)F * H, (size_t)H * H));
@@ -1039,13 +959,38 @@ struct LlamaGPU : public ffmi_model {
         allocs.erase(it);
         break;
       }
-#undef TRY
     return FFMI_OK;
   }
 
-  ffmi_status allreduce(uint16_t *buf, size_t n) {
-    if (o.tp_size <= 1) return FFMI_OK;
-    return ffmi_allreduce(o.comm, buf, buf, n, FFMI_F16, (ffmi_stream)stream);
+  // Chunk ch of a row-parallel GEMM computed in tp_chunks column chunks: its
+  // GEMM on `stream` into *cb (a chunk = Hc / 16 consecutive tiles of the
+  // H / 16 per k-row), then comm_stream waits for it, so the caller's
+  // collective on comm_stream runs while the next chunk computes.  Over the
+  // transport the chunk's split-K slabs (its own workspace region) are left in
+  // *part for the collective's copy-in, with no reduce pass on this stream.
+  // (FFMI_FAULT_TP_AR_DROP: the chunk zeroed before it is handed over)
+  ffmi_status rowpar_chunk(const uint16_t *X, const uint16_t *W, int K, int T, int XP, int ch,
+                           uint16_t **cb, ffmi::Partials *part) {
+    const int H = c.hidden, Hc = H / tp_chunks;
+    const size_t tiles = (size_t)(Hc / 16) * ffmi::w_tile_stride((K + 31) / 32);
+    const bool drop = ar_drop_now;
+    // (the norm variant runs over the transport only: peer is implied there)
+    const bool def = peer && ar_slabs && !drop;
+    *cb = chunk_buf + (size_t)ch * T * Hc;
+    FFMI_HIP(ffmi::launch_gemm(X, W + ch * tiles, *cb,
+                               def ? (float *)((char *)ws + ch * ws_chunk) : ws,
+                               def ? ws_chunk : ws_bytes, T, Hc, K, XP, stream,
+                               def ? part : nullptr, H / 16));
+    if (drop) FFMI_HIP(hipMemsetAsync(*cb, 0, (size_t)T * Hc * 2, stream));
+    FFMI_HIP(hipEventRecord(ev_chunk[ch], stream));
+    FFMI_HIP(hipStreamWaitEvent(comm_stream, ev_chunk[ch], 0));
+    return FFMI_OK;
+  }
+  // `stream` behind the chunks' collectives
+  ffmi_status rowpar_join() {
+    FFMI_HIP(hipEventRecord(ev_comm_done, comm_stream));
+    FFMI_HIP(hipStreamWaitEvent(stream, ev_comm_done, 0));
+    return FFMI_OK;
   }
 
   // Row-parallel GEMM + sum all-reduce into `out` [T][H] (model.cc:3421-3445).
@@ -1055,9 +1000,9 @@ struct LlamaGPU : public ffmi_model {
   ffmi_status rowpar_gemm_allreduce(const uint16_t *X, const uint16_t *W, int K, uint16_t *out,
                                     int T, int XP) {
     const int H = c.hidden;
-    // (FFMI_FAULT_TP_AR_DROP: the GEMM's output zeroed before the all-reduce)
-    const bool drop = ar_drop_now;
     if (!(peer || rccl) || tp_chunks == 1) {
+      // (FFMI_FAULT_TP_AR_DROP: the GEMM's output zeroed before the all-reduce)
+      const bool drop = ar_drop_now;
       // over the transport the split-K reduce is the all-reduce's copy-in
       ffmi::Partials part;
       FFMI_HIP(ffmi::launch_gemm(X, W, out, ws, ws_bytes, T, H, K, XP, stream,
@@ -1066,39 +1011,23 @@ struct LlamaGPU : public ffmi_model {
       if (peer)
         return ffmi::comm_allreduce_cols(o.comm, out, out, T, H, H, 0, FFMI_F16, stream,
                                          part.S > 0 ? &part : nullptr);
-      return allreduce(out, (size_t)T * H);
+      return ffmi_allreduce(o.comm, out, out, (size_t)T * H, FFMI_F16, (ffmi_stream)stream);
     }
     const int Hc = H / tp_chunks;
-    // a chunk = Hc / 16 consecutive tiles of the H / 16 per k-row
-    const size_t tiles = (size_t)(Hc / 16) * ffmi::w_tile_stride((K + 31) / 32);
     for (int ch = 0; ch < tp_chunks; ++ch) {
-      uint16_t *cb = chunk_buf + (size_t)ch * T * Hc;
-      // over the transport: the chunk's split-K slabs (own workspace region)
-      // go to the all-reduce's copy-in, no reduce pass on this stream
+      uint16_t *cb;
       ffmi::Partials part;
-      const bool def = peer && ar_slabs && !drop;
-      FFMI_HIP(ffmi::launch_gemm(X, W + ch * tiles, cb,
-                                 def ? (float *)((char *)ws + ch * ws_chunk) : ws,
-                                 def ? ws_chunk : ws_bytes, T, Hc, K, XP, stream,
-                                 def ? &part : nullptr, H / 16));
-      if (drop) FFMI_HIP(hipMemsetAsync(cb, 0, (size_t)T * Hc * 2, stream));
-      FFMI_HIP(hipEventRecord(ev_chunk[ch], stream));
-      FFMI_HIP(hipStreamWaitEvent(comm_stream, ev_chunk[ch], 0));
+      TRY(rowpar_chunk(X, W, K, T, XP, ch, &cb, &part));
       if (peer) {  // the transport reduces straight into out's columns
-        ffmi_status st = ffmi::comm_allreduce_cols(o.comm, cb, out, T, Hc, H, ch * Hc, FFMI_F16,
-                                                   comm_stream, part.S > 0 ? &part : nullptr);
-        if (st != FFMI_OK) return st;
+        TRY(ffmi::comm_allreduce_cols(o.comm, cb, out, T, Hc, H, ch * Hc, FFMI_F16, comm_stream,
+                                      part.S > 0 ? &part : nullptr));
       } else {  // RCCL: contiguous in place, then into out's columns
-        ffmi_status st = ffmi_allreduce(o.comm, cb, cb, (size_t)T * Hc, FFMI_F16,
-                                        (ffmi_stream)comm_stream);
-        if (st != FFMI_OK) return st;
+        TRY(ffmi_allreduce(o.comm, cb, cb, (size_t)T * Hc, FFMI_F16, (ffmi_stream)comm_stream));
         FFMI_HIP(hipMemcpy2DAsync(out + (size_t)ch * Hc, (size_t)H * 2, cb, (size_t)Hc * 2,
                                   (size_t)Hc * 2, T, hipMemcpyDeviceToDevice, comm_stream));
       }
     }
-    FFMI_HIP(hipEventRecord(ev_comm_done, comm_stream));
-    FFMI_HIP(hipStreamWaitEvent(stream, ev_comm_done, 0));
-    return FFMI_OK;
+    return rowpar_join();
   }
 
   // rowpar_gemm_allreduce with the residual norm after it folded into the
@@ -1111,9 +1040,9 @@ struct LlamaGPU : public ffmi_model {
                                          const uint16_t *wnorm) {
     const int H = c.hidden;
     const float eps = c.rms_eps;
-    const bool drop = ar_drop_now;
     const bool two = ffmi::comm_two_shot(o.comm, (size_t)T * H * 2);
     if (tp_chunks == 1) {
+      const bool drop = ar_drop_now;
       ffmi::Partials part;
       FFMI_HIP(ffmi::launch_gemm(X, W, proj, ws, ws_bytes, T, H, K, XP, stream,
                                  ar_slabs && !drop ? &part : nullptr));
@@ -1122,36 +1051,23 @@ struct LlamaGPU : public ffmi_model {
                                        two, stream, part.S > 0 ? &part : nullptr);
     }
     const int Hc = H / tp_chunks;
-    const size_t tiles = (size_t)(Hc / 16) * ffmi::w_tile_stride((K + 31) / 32);
     const int nr = ffmi::comm_size(o.comm), rk = ffmi::comm_rank(o.comm);
     for (int ch = 0; ch < tp_chunks; ++ch) {
-      uint16_t *cb = chunk_buf + (size_t)ch * T * Hc;
+      uint16_t *cb;
       ffmi::Partials part;
-      const bool def = ar_slabs && !drop;
-      FFMI_HIP(ffmi::launch_gemm(X, W + ch * tiles, cb,
-                                 def ? (float *)((char *)ws + ch * ws_chunk) : ws,
-                                 def ? ws_chunk : ws_bytes, T, Hc, K, XP, stream,
-                                 def ? &part : nullptr, H / 16));
-      if (drop) FFMI_HIP(hipMemsetAsync(cb, 0, (size_t)T * Hc * 2, stream));
-      FFMI_HIP(hipEventRecord(ev_chunk[ch], stream));
-      FFMI_HIP(hipStreamWaitEvent(comm_stream, ev_chunk[ch], 0));
+      TRY(rowpar_chunk(X, W, K, T, XP, ch, &cb, &part));
       const ffmi::Partials *sl = part.S > 0 ? &part : nullptr;
-      ffmi_status st;
-      if (ch + 1 < tp_chunks) {  // columns [ch Hc, (ch+1) Hc) of the sum into proj
-        st = two ? ffmi::comm_reduce_rows(o.comm, cb, proj, T, Hc, H, ch * Hc,
-                                          (int)((long)T * rk / nr), (int)((long)T * (rk + 1) / nr),
-                                          comm_stream, sl)
-                 : ffmi::comm_allreduce_cols(o.comm, cb, proj, T, Hc, H, ch * Hc, FFMI_F16,
-                                             comm_stream, sl);
-      } else {
-        st = ffmi::comm_allreduce_norm(o.comm, cb, T, H, ch * Hc, proj, res, wnorm, eps, h, packed,
-                                       two, comm_stream, sl);
-      }
-      if (st != FFMI_OK) return st;
+      if (ch + 1 < tp_chunks)  // columns [ch Hc, (ch+1) Hc) of the sum into proj
+        TRY(two ? ffmi::comm_reduce_rows(o.comm, cb, proj, T, Hc, H, ch * Hc,
+                                         (int)((long)T * rk / nr), (int)((long)T * (rk + 1) / nr),
+                                         comm_stream, sl)
+                : ffmi::comm_allreduce_cols(o.comm, cb, proj, T, Hc, H, ch * Hc, FFMI_F16,
+                                            comm_stream, sl));
+      else
+        TRY(ffmi::comm_allreduce_norm(o.comm, cb, T, H, ch * Hc, proj, res, wnorm, eps, h, packed,
+                                      two, comm_stream, sl));
     }
-    FFMI_HIP(hipEventRecord(ev_comm_done, comm_stream));
-    FFMI_HIP(hipStreamWaitEvent(stream, ev_comm_done, 0));
-    return FFMI_OK;
+    return rowpar_join();
   }
 
   // One step over the packed batch; k = results per token.  Small batches
@@ -1172,7 +1088,7 @@ struct LlamaGPU : public ffmi_model {
   // the next step read the half this one wrote); kept here so graph replays
   // and eager steps agree
   int tree_parity = 0;
-  std::map<GraphKey, hipGraphExec_t> graphs;
+  GraphCache<GraphKey> graphs{512};
   // FFMI_CHAIN_GROUP=g (>= 2): chained beam slots 1 .. kChain-2 are staged and
   // go out g per graph launch (slot kChain-1 alone, behind the collect event):
   // the boundary between two graph launches (4.9 us from one step's last
@@ -1184,12 +1100,11 @@ struct LlamaGPU : public ffmi_model {
   // tokens/s
   int chain_group = getenv("FFMI_CHAIN_GROUP") ? atoi(getenv("FFMI_CHAIN_GROUP")) : kChain - 2;
   struct PendingSlot {
-    int slot, T, k;
-    size_t bytes;
+    Step step;
     GraphKey key;
   };
   std::vector<PendingSlot> pend;  // staged, not yet launched (grouped slots)
-  std::map<std::vector<GraphKey>, hipGraphExec_t> group_graphs;
+  GraphCache<std::vector<GraphKey>> group_graphs{256};
   bool use_graphs = getenv("FFMI_NO_GRAPHS") == nullptr;
   bool blob_fetch = !getenv("FFMI_BLOB_FETCH") || atoi(getenv("FFMI_BLOB_FETCH")) != 0;
   // largest one-item-per-request step that is graphed (FFMI_GRAPH_MAXT: A/B)
@@ -1209,12 +1124,56 @@ struct LlamaGPU : public ffmi_model {
   std::map<int, StepTime> st_sum;
   int st_T = 0;
   ffmi_status forward(int k) {
-    ffmi_status st = forward_launch(k);
-    if (st != FFMI_OK) return st;
+    TRY(forward_launch(k, 0));
     return forward_finish();
   }
 
-  ffmi_status forward_launch(int k) {
+  // a side array behind what is staged in b so far (16-byte aligned pieces)
+  template <typename E>
+  static ffmi_status stage_extra(StepExtra<E> *x, int T, ffmi_batch_dev *b, size_t *bytes) {
+    x->off = *bytes;
+    const size_t n = ((size_t)T * sizeof(E) + 15) & ~(size_t)15;
+    FFMI_CHECK((int)x->v.size() == T && *bytes + n <= b->cap, FFMI_ERR_INVALID);
+    memcpy(b->host + *bytes, x->v.data(), (size_t)T * sizeof(E));
+    *bytes += n;
+    return FFMI_OK;
+  }
+
+  // Stage the packed batch (ps) as the step of `slot`, k results per token:
+  // the records, then the side arrays that are switched on -- draws, targets,
+  // adapter ids, in that order.  A BEAM step never has any: set_sampling and
+  // set_logprobs refuse a BEAM model and creation refuses FFMI_MODEL_LORA on
+  // one, so a chained or grouped slot's blob is its records alone and its key
+  // has lora_any = 0.  *key is set for a step with rows only.
+  ffmi_status stage_step(int k, int slot, Step *s, GraphKey *key) {
+    const int T = (int)ps.tokens.size();
+    ffmi_batch_dev *b = chain_batch[slot];
+    ffmi_batch_desc desc;
+    ps.desc(&desc);
+    // the embedding gather indexes the table by token id: reject bad ids on
+    // the host instead of reading out of bounds on the device
+    // (a chained beam step's -1 - i: entry i of the previous slot's ids,
+    // themselves top-k picks in range)
+    const long prev_n = slot > 0 ? (long)slot_results[slot - 1] : 0;
+    for (int t = 0; t < T; ++t)
+      FFMI_CHECK((desc.tokens[t].token_id >= 0 && desc.tokens[t].token_id < c.vocab_size) ||
+                     (desc.tokens[t].token_id < 0 && -1L - desc.tokens[t].token_id < prev_n),
+                 FFMI_ERR_INVALID);
+    size_t bytes = 0;
+    TRY(ffmi::batch_stage(b, &desc, &bytes));
+    *s = Step{b, slot, T, k, bytes};
+    if (T == 0) return FFMI_OK;
+    if (sampling) TRY(stage_extra(&step_u, T, b, &bytes));
+    if (logprobs) TRY(stage_extra(&step_targets, T, b, &bytes));
+    if (lora) TRY(stage_extra(&step_slots, T, b, &bytes));
+    s->blob_bytes = bytes;
+    *key = GraphKey{T, b->num_work, b->num_commits, k, tree_parity, b->commit_overlap ? 1 : 0,
+                    (b->one_item_per_req ? 1 : 0) | (b->lds_tail ? 2 : 0), b->max_q, slot, bytes,
+                    lora && step_lora_any ? 1 : 0};
+    return FFMI_OK;
+  }
+
+  ffmi_status forward_launch(int k, int slot) {
     inflight = false;
     const int T = (int)ps.tokens.size();
     if (step_timing) {
@@ -1226,62 +1185,27 @@ struct LlamaGPU : public ffmi_model {
       st_T = T;
     }
     prof_this_step = prof_level == 1 && (prof_steps++ % prof_every) == 0;
-    ffmi_batch_desc desc;
-    ps.desc(&desc);
-    // the embedding gather indexes the table by token id: reject bad ids on
-    // the host instead of reading out of bounds on the device
-    // (a chained beam step's -1 - i: entry i of the previous slot's ids,
-    // themselves top-k picks in range)
-    const long prev_n = cur_slot > 0 ? (long)slot_results[cur_slot - 1] : 0;
-    for (int t = 0; t < T; ++t)
-      FFMI_CHECK((desc.tokens[t].token_id >= 0 && desc.tokens[t].token_id < c.vocab_size) ||
-                     (desc.tokens[t].token_id < 0 && -1L - desc.tokens[t].token_id < prev_n),
-                 FFMI_ERR_INVALID);
-    size_t bytes = 0;
-    ffmi_status st = ffmi::batch_stage(batch, &desc, &bytes);
-    if (st != FFMI_OK) return st;
+    Step step;
+    GraphKey key{};
+    TRY(stage_step(k, slot, &step, &key));
     if (T == 0) return FFMI_OK;
-    if (sampling && (st = stage_step_u(T, &bytes)) != FFMI_OK) return st;
-    if (logprobs && (st = stage_step_targets(T, &bytes)) != FFMI_OK) return st;
-    if (lora && (st = stage_step_slots(T, &bytes)) != FFMI_OK) return st;
-    probs_h = reinterpret_cast<float *>(ids_h + cur_slot * slot_ints() + (size_t)T * k);
     // graphed: small steps, and tree-verify steps of one work item per
     // request (a fixed shape while the batch is full: T = 168 for 8 requests
     // of 21 tree tokens); prefill blocks stay eager (one-off shapes)
-    const bool graph = use_graphs && !dbg && (T <= 64 || (batch->one_item_per_req && T <= graph_max_t)) &&
+    const bool graph = use_graphs && !dbg &&
+                       (T <= 64 || (step.batch->one_item_per_req && T <= graph_max_t)) &&
                        (o.tp_size == 1 || peer || rccl || ffmi::comm_size(o.comm) == 1) &&
                        !prof_on(0, T) &&
                        !prof_on(c.num_layers / 2, T);
-    if (graph) {
-      const GraphKey key{T, batch->num_work, batch->num_commits, k, tree_parity,
-                         batch->commit_overlap ? 1 : 0,
-                         (batch->one_item_per_req ? 1 : 0) | (batch->lds_tail ? 2 : 0),
-                         batch->max_q, cur_slot, bytes, lora && step_lora_any ? 1 : 0};
-      auto it = graphs.find(key);
-      if (it == graphs.end()) {
-        if (graphs.size() >= 512) clear_graphs();
-        hipGraph_t g = nullptr;
-        FFMI_HIP(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-        st = enqueue(k, bytes, false, T);
-        const hipError_t ce = hipStreamEndCapture(stream, &g);
-        if (st != FFMI_OK || ce != hipSuccess) {
-          if (g) (void)hipGraphDestroy(g);
-          if (st != FFMI_OK) return st;
-          FFMI_HIP(ce);
-        }
-        hipGraphExec_t ex = nullptr;
-        const hipError_t ie = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(g);
-        FFMI_HIP(ie);
-        it = graphs.emplace(key, ex).first;
-      }
-      if (step_timing) FFMI_HIP(hipEventRecord(st_ev[0], stream));
-      FFMI_HIP(hipGraphLaunch(it->second, stream));
-    } else {
-      if (step_timing) FFMI_HIP(hipEventRecord(st_ev[0], stream));
-      st = enqueue(k, bytes, true, T);
-      if (st != FFMI_OK) return st;
+    hipGraphExec_t ex = nullptr;
+    if (graph && !(ex = graphs.find(key))) {
+      if (graphs.full()) clear_graphs();
+      TRY(capture_graph(stream, [&] { return enqueue(step, false); }, &ex));
+      graphs.insert(key, ex);
     }
+    if (step_timing) FFMI_HIP(hipEventRecord(st_ev[0], stream));
+    if (graph) FFMI_HIP(hipGraphLaunch(ex, stream));
+    else TRY(enqueue(step, true));
     if (step_timing) {
       FFMI_HIP(hipEventRecord(st_ev[1], stream));
       st_t1 = now_us();
@@ -1290,61 +1214,36 @@ struct LlamaGPU : public ffmi_model {
     return FFMI_OK;
   }
 
-  // A chained slot staged for a grouped launch (chain_group): the staging
-  // half of forward_launch; flush_pending captures / replays the group.
+  // A chained slot staged for a grouped launch (chain_group); flush_pending
+  // captures / replays the group.
   ffmi_status stage_pending(int k, int slot) {
-    const int T = (int)ps.tokens.size();
-    ffmi_batch_desc desc;
-    ps.desc(&desc);
-    const long prev_n = slot > 0 ? (long)slot_results[slot - 1] : 0;
-    for (int t = 0; t < T; ++t)
-      FFMI_CHECK((desc.tokens[t].token_id >= 0 && desc.tokens[t].token_id < c.vocab_size) ||
-                     (desc.tokens[t].token_id < 0 && -1L - desc.tokens[t].token_id < prev_n),
-                 FFMI_ERR_INVALID);
-    size_t bytes = 0;
-    ffmi_status st = ffmi::batch_stage(batch, &desc, &bytes);
-    if (st != FFMI_OK) return st;
-    pend.push_back({slot, T, k, bytes,
-                    GraphKey{T, batch->num_work, batch->num_commits, k, tree_parity,
-                             batch->commit_overlap ? 1 : 0,
-                             (batch->one_item_per_req ? 1 : 0) | (batch->lds_tail ? 2 : 0),
-                             batch->max_q, slot, bytes}});
-    return FFMI_OK;
+    PendingSlot q{};
+    const ffmi_status st = stage_step(k, slot, &q.step, &q.key);
+    if (st == FFMI_OK) pend.push_back(q);
+    return st;
   }
   ffmi_status flush_pending() {
     if (pend.empty()) return FFMI_OK;
     std::vector<GraphKey> keys;
     for (const auto &q : pend) keys.push_back(q.key);
-    auto it = group_graphs.find(keys);
-    if (it == group_graphs.end()) {
-      if (group_graphs.size() >= 256) clear_graphs();
-      hipGraph_t g = nullptr;
-      ffmi_status st = FFMI_OK;
-      FFMI_HIP(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-      for (const auto &q : pend) {
-        cur_slot = q.slot;
-        batch = chain_batch[q.slot];
-        st = enqueue(q.k, q.bytes, false, q.T);
-        if (st != FFMI_OK) break;
-      }
-      cur_slot = 0;
-      batch = chain_batch[0];
-      const hipError_t ce = hipStreamEndCapture(stream, &g);
-      if (st != FFMI_OK || ce != hipSuccess) {
-        if (g) (void)hipGraphDestroy(g);
+    hipGraphExec_t ex = group_graphs.find(keys);
+    if (!ex) {
+      if (group_graphs.full()) clear_graphs();
+      const ffmi_status st = capture_graph(stream, [&]() -> ffmi_status {
+        for (const auto &q : pend) {
+          const ffmi_status e = enqueue(q.step, false);
+          if (e != FFMI_OK) return e;
+        }
+        return FFMI_OK;
+      }, &ex);
+      if (st != FFMI_OK) {
         pend.clear();
-        if (st != FFMI_OK) return st;
-        FFMI_HIP(ce);
+        return st;
       }
-      hipGraphExec_t ex = nullptr;
-      const hipError_t ie = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
-      (void)hipGraphDestroy(g);
-      if (ie != hipSuccess) pend.clear();
-      FFMI_HIP(ie);
-      it = group_graphs.emplace(keys, ex).first;
+      group_graphs.insert(keys, ex);
     }
     pend.clear();
-    FFMI_HIP(hipGraphLaunch(it->second, stream));
+    FFMI_HIP(hipGraphLaunch(ex, stream));
     inflight = true;
     return FFMI_OK;
   }
@@ -1377,20 +1276,17 @@ struct LlamaGPU : public ffmi_model {
   }
 
   void clear_graphs() {
-    for (auto &kv : graphs) (void)hipGraphExecDestroy(kv.second);
     graphs.clear();
-    for (auto &kv : group_graphs) (void)hipGraphExecDestroy(kv.second);
     group_graphs.clear();
   }
 
   // everything a step puts on the stream (no host synchronisation inside)
-  ffmi_status enqueue(int k, size_t blob_bytes, bool record_upload, int T) {
-    const int H = c.hidden, V = c.vocab_size;
+  ffmi_status enqueue(const Step &step, bool record_upload) {
+    const int H = c.hidden, V = c.vocab_size, T = step.T;
+    ffmi_batch_dev *const batch = step.batch;
+    const size_t blob_bytes = step.blob_bytes;
     const float eps = c.rms_eps;
     const ffmi_stream s = (ffmi_stream)stream;
-    ffmi_status st;
-#define TRY(x) \
-  do { if ((st = (x)) != FFMI_OK) return st; } while (0)
     // the step's blob: fetched by the first kernel from the mapped staging
     // (default), or a separate H2D copy (FFMI_BLOB_FETCH=0: A/B)
     if (!blob_fetch) TRY(ffmi::batch_copy(batch, blob_bytes, stream, record_upload));
@@ -1454,8 +1350,7 @@ struct LlamaGPU : public ffmi_model {
                                       l == 0 ? ffmi::Partials() : down_part,
                                       l == 0 ? (blob_fetch ? batch->host : batch->dev) : nullptr,
                                       l == 0 && blob_fetch ? batch->dev : nullptr, blob_bytes,
-                                      cur_slot > 0 ? ids_dev + (size_t)(cur_slot - 1) * (slot_ints() / 2)
-                                                   : nullptr));
+                                      step.slot > 0 ? slot_ids_dev(step.slot - 1) : nullptr));
         // the staging is free for the next step once the fetch has read it
         if (l == 0 && blob_fetch && record_upload) FFMI_HIP(hipEventRecord(batch->uploaded, stream));
         prof_end(pr, NORM, (double)T * H * 2 * (l == 0 ? 3 : 4), 0);
@@ -1553,7 +1448,7 @@ struct LlamaGPU : public ffmi_model {
             down_part = ffmi::Partials();
           }
           FFMI_HIP(ffmi::launch_lora(mlp, T, Fl, H,
-                                     reinterpret_cast<const int32_t *>(batch->dev + step_slots_off),
+                                     reinterpret_cast<const int32_t *>(batch->dev + step_slots.off),
                                      lora_tab + (size_t)l * FFMI_LORA_MAX_ADAPTERS, proj, packed,
                                      lora_ws, nullptr, stream));
           prof_end(pr, LORA, 2.0 * FFMI_LORA_MAX_RANK * ((double)Fl + H) + 4.0 * T * H, 0);
@@ -1600,44 +1495,41 @@ struct LlamaGPU : public ffmi_model {
     prof_end(pr, GEMM_LM_HEAD, gemm_bytes(T, Vl, Vl, H), 2.0 * T * Vl * H);
     mkt();
     pr = prof_begin(ptail);
-    TRY(enqueue_sampling(k, T));
+    TRY(enqueue_sampling(step));
     prof_end(pr, SAMPLING, (double)T * V * 2, 0);
     mkt();
     if (logprobs) {
       pr = prof_begin(ptail);
-      TRY(enqueue_logprobs(k, T));
+      TRY(enqueue_logprobs(step));
       prof_end(pr, LOGPROBS, (double)T * V * 2, 0);
     }
-#undef TRY
     return FFMI_OK;
   }
 
   // softmax + argmax / arg-top-k of the step's logits into the pinned results
-  ffmi_status enqueue_sampling(int k, int T) {
-    const int V = c.vocab_size;
+  ffmi_status enqueue_sampling(const Step &step) {
+    const int V = c.vocab_size, T = step.T, k = step.k;
+    const ffmi_batch_dev *batch = step.batch;
     const ffmi_stream s = (ffmi_stream)stream;
-    ffmi_status st;
-#define TRY(x) \
-  do { if ((st = (x)) != FFMI_OK) return st; } while (0)
     // ids [T*k] then probs [T*k] back to back.  The sampling kernel writes
     // them straight into the pinned host buffer (a few bytes per row over
     // PCIe, visible after the stream synchronisation like a copy kernel's
     // stores), so a step needs no result-copy launch; FFMI_RESULT_COPY=1
     // keeps the device buffer + copy (A/B runs)
-    int32_t *ids_o = result_copy ? ids_d : ids_h + cur_slot * slot_ints();
+    int32_t *ids_o = result_copy ? ids_d : slot_ids_h(step.slot);
     float *probs_o = reinterpret_cast<float *>(ids_o + (size_t)T * k);
     if (sampling && Vl != V) {
       // sharded top-p: five record exchanges; every rank staged the same u
       FFMI_CHECK(k == 1 && sample_ws, FFMI_ERR_INVALID);
       TRY(ffmi_vocab_shard_sample_topp(
           o.comm, logits, T, Vl, temperature, topp,
-          reinterpret_cast<const float *>(batch->dev + step_u_off), ids_o, probs_o, sample_ws,
+          reinterpret_cast<const float *>(batch->dev + step_u.off), ids_o, probs_o, sample_ws,
           sample_ws_bytes, s));
     } else if (sampling) {
       // (set_sampling: INC; u behind the blob's records)
       FFMI_CHECK(k == 1 && sample_ws, FFMI_ERR_INVALID);
       FFMI_HIP(ffmi::launch_sample_topp(
-          logits, T, V, temperature, topp, reinterpret_cast<const float *>(batch->dev + step_u_off),
+          logits, T, V, temperature, topp, reinterpret_cast<const float *>(batch->dev + step_u.off),
           ids_o, probs_o, sample_ws, ffmi::sample_topp_workspace_bytes(T, V), stream));
     } else if (Vl != V) {
       // sharded softmax / top-k: three record exchanges, then the merge
@@ -1648,13 +1540,12 @@ struct LlamaGPU : public ffmi_model {
       FFMI_CHECK(k >= 1 && k <= 4 && k <= V, FFMI_ERR_INVALID);
       FFMI_HIP(ffmi::launch_argmax(logits, T, V, k, ids_o, probs_o, stream, topk_ws, topk_ws_bytes,
                                    mode == FFMI_MODEL_BEAM
-                                       ? ids_dev + (size_t)cur_slot * (slot_ints() / 2)
+                                       ? slot_ids_dev(step.slot)
                                        : logprobs ? lp_picks : nullptr));
     }
     if (result_copy)
-      FFMI_HIP(hipMemcpyAsync(ids_h + cur_slot * slot_ints(), ids_d, (size_t)T * k * 8,
+      FFMI_HIP(hipMemcpyAsync(slot_ids_h(step.slot), ids_d, (size_t)T * k * 8,
                               hipMemcpyDeviceToHost, stream));
-#undef TRY
     return FFMI_OK;
   }
 
@@ -1662,13 +1553,14 @@ struct LlamaGPU : public ffmi_model {
   // (set_logprobs: INC / TREE, Vl == V, k = 1; targets behind the blob's
   // records and draws.  The picks: the argmax's device copy, or the pick's ids
   // output itself -- pinned under do_sample, ids_d with a result copy)
-  ffmi_status enqueue_logprobs(int k, int T) {
+  ffmi_status enqueue_logprobs(const Step &step) {
+    const int k = step.k;
     FFMI_CHECK(k == 1 && lp_ws, FFMI_ERR_INVALID);
     const int32_t *picks = result_copy ? ids_d
-                           : sampling  ? ids_h + cur_slot * slot_ints()
+                           : sampling  ? slot_ids_h(step.slot)
                                        : lp_picks;
-    return ffmi_token_logprobs(logits, T, c.vocab_size, sampling ? temperature : 0.f,
-                               reinterpret_cast<const int32_t *>(batch->dev + step_targets_off),
+    return ffmi_token_logprobs(logits, step.T, c.vocab_size, sampling ? temperature : 0.f,
+                               reinterpret_cast<const int32_t *>(step.batch->dev + step_targets.off),
                                picks, lp_h, lp_ws, lp_ws_bytes, (ffmi_stream)stream);
   }
 
@@ -1679,9 +1571,7 @@ struct LlamaGPU : public ffmi_model {
     if (sampling) draw_step_u(bc);
     if (logprobs) take_step_targets(bc);
     if (lora) take_step_slots(bc);
-    cur_slot = 0;
-    ffmi_status st = forward(1);
-    if (st != FFMI_OK) return st;
+    TRY(forward(1));
     memcpy(ir->token_ids, ids_h, bc.num_tokens * sizeof(int32_t));
     if (logprobs) memcpy(ir->logprobs, lp_h, bc.num_tokens * sizeof(float));
     return FFMI_OK;
@@ -1692,16 +1582,13 @@ struct LlamaGPU : public ffmi_model {
     pack_tree(bc, o.max_requests, slots, &ps);
     if (logprobs) take_step_targets(bc);
     if (lora) take_step_slots(bc);
-    cur_slot = 0;
-    ffmi_status st = forward(1);
-    if (st != FFMI_OK) return st;
+    TRY(forward(1));
     memcpy(ir->token_ids, ids_h, bc.num_tokens * sizeof(int32_t));
     if (logprobs) memcpy(ir->logprobs, lp_h, bc.num_tokens * sizeof(float));
     return FFMI_OK;
   }
   ffmi_status run_beam(const BeamSearchBatchConfig &bc, BeamInferenceResult *ir) override {
-    ffmi_status st = beam_launch(bc);
-    if (st != FFMI_OK) return st;
+    TRY(beam_launch(bc));
     return beam_collect(ir);
   }
   ffmi_status beam_launch(const BeamSearchBatchConfig &bc) override {
@@ -1716,12 +1603,7 @@ struct LlamaGPU : public ffmi_model {
     if (mode != FFMI_MODEL_BEAM) return FFMI_ERR_INVALID;
     FFMI_CHECK(bc.num_tokens <= o.max_tokens && slot >= 0 && slot < kChain, FFMI_ERR_INVALID);
     FFMI_CHECK(slot == 0 || can_chain_beam(), FFMI_ERR_INVALID);
-    if (!chain_batch[slot]) {
-      ffmi_batch_dev *b = nullptr;
-      ffmi_status st = ffmi_batch_create((o.max_tokens + 15) & ~15, o.max_requests, &b);
-      if (st != FFMI_OK) return st;
-      chain_batch[slot] = b;
-    }
+    FFMI_CHECK(chain_batch[slot], FFMI_ERR_INVALID);
     pack_beam(bc, o.max_requests, slots, &ps);
     // a chained step's -1 - i (scheduler entry i of the previous slot) ->
     // -1 - its [T][k] index, which the gather reads from device memory
@@ -1736,8 +1618,6 @@ struct LlamaGPU : public ffmi_model {
       if (!chain_t0) FFMI_HIP(hipEventCreate(&chain_t0));
       FFMI_HIP(hipEventRecord(chain_t0, stream));
     }
-    cur_slot = slot;
-    batch = chain_batch[slot];
     slot_results[slot] = (size_t)bc.num_tokens * k;
     beam_result_layout(bc, &slot_map[slot]);
     // grouped (chain_group): slots 1 .. kChain-2 staged, launched g at a time
@@ -1748,21 +1628,12 @@ struct LlamaGPU : public ffmi_model {
     ffmi_status st;
     if (grp) {
       st = stage_pending(k, slot);
-      if (st == FFMI_OK && ((slot - 1) % chain_group == chain_group - 1 || slot == kChain - 2)) {
-        cur_slot = 0;
-        batch = chain_batch[0];
+      if (st == FFMI_OK && ((slot - 1) % chain_group == chain_group - 1 || slot == kChain - 2))
         st = flush_pending();
-      }
     } else {
-      cur_slot = 0;
-      batch = chain_batch[0];
       st = flush_pending();
-      cur_slot = slot;
-      batch = chain_batch[slot];
-      if (st == FFMI_OK) st = forward_launch(k);
+      if (st == FFMI_OK) st = forward_launch(k, slot);
     }
-    batch = chain_batch[0];
-    cur_slot = 0;
     // Events let the scheduler replay slot d's bookkeeping while later slots
     // run.  One behind every slot cost the GPU more than the replay it
     // overlapped (same-box A/B, tokens/s: 1333 with, 1342 with none, 1326
@@ -1779,16 +1650,12 @@ struct LlamaGPU : public ffmi_model {
         FFMI_HIP(hipEventCreateWithFlags(&slot_ev[slot], step_timing ? 0 : hipEventDisableTiming));
       FFMI_HIP(hipEventRecord(slot_ev[slot], stream));
       slot_ev_live[slot] = true;
-      last_slot = slot;
     }
     return st;
   }
   ffmi_status beam_collect_chained(int slot, BeamInferenceResult *ir) override {
     FFMI_CHECK(slot >= 0 && slot < kChain, FFMI_ERR_INVALID);
-    {  // (grouped slots still staged go out first)
-      ffmi_status st = flush_pending();
-      if (st != FFMI_OK) return st;
-    }
+    TRY(flush_pending());  // (grouped slots still staged go out first)
     int ev = -1;  // the first live event at or after this slot, before the last
     for (int e = slot; e < last_slot && ev < 0; ++e)
       if (slot_ev_live[e] && slot_ev[e]) ev = e;
@@ -1797,8 +1664,7 @@ struct LlamaGPU : public ffmi_model {
       FFMI_HIP(hipEventSynchronize(slot_ev[ev]));
     } else {
       const int ls = last_slot;
-      ffmi_status st = forward_finish();  // (every launched step: one stream)
-      if (st != FFMI_OK) return st;
+      TRY(forward_finish());  // (every launched step: one stream)
       for (bool &b : slot_ev_live) b = false;
       // FFMI_STEP_TIMING: the GPU span of a whole chain, from the event before
       // slot 0's launch to the one after the last slot
@@ -1813,7 +1679,7 @@ struct LlamaGPU : public ffmi_model {
       last_slot = -1;
     }
     const size_t n = slot_results[slot];
-    const int32_t *ids = ids_h + slot * slot_ints();
+    const int32_t *ids = slot_ids_h(slot);
     const float *pr = reinterpret_cast<const float *>(ids + n);
     const std::vector<int> &map = slot_map[slot];
     for (size_t i = 0; i < map.size(); ++i) {

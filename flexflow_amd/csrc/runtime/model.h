@@ -10,6 +10,7 @@
 
 #include "../ffmi_internal.h"
 #include "batch_config.h"
+#include "tensor_file.h"
 
 namespace ffmi {
 
@@ -182,6 +183,13 @@ bool lora_id_release(const void *owner, int id);      // false: not the owner's,
 void lora_id_release_all(const void *owner);          // (a model going away)
 bool lora_id_loaded(int id);
 void lora_id_ref(int id, int delta);
+// a tensor file's outcome as a status, "<what> not found: <path>" / "<what> has
+// the wrong size: <path>" left as the last error
+inline ffmi_status tensor_status(TensorRead r, const char *what, const std::string &path) {
+  if (r == TensorRead::ok) return FFMI_OK;
+  ffmi_set_last_error(tensor_read_message(r, what, path).c_str(), __FILE__, __LINE__);
+  return FFMI_ERR_INVALID;
+}
 ffmi_status create_llama_gpu(const ffmi_llama_config *cfg, const ffmi_model_opts *o,
                              ffmi_model **out, unsigned flags = 0);  // (FFMI_MODEL_* bits)
 // full precision (--use-full-precision): runtime/llama_f32.cpp
