@@ -78,6 +78,9 @@ def llama_config_from_hf(src: Union[str, Mapping]) -> dict:
 
 
 _PEFT_PREFIX = "base_model.model.model."
+# the served target modules and the block each lives in
+_PEFT_SERVED = {"q_proj": "self_attn", "k_proj": "self_attn", "v_proj": "self_attn",
+                "o_proj": "self_attn", "down_proj": "mlp"}
 
 
 def convert_peft_adapter(state_dict: Mapping, adapter_config: Mapping, dst_folder: str,
@@ -86,25 +89,34 @@ def convert_peft_adapter(state_dict: Mapping, adapter_config: Mapping, dst_folde
     return ``(rank, alpha)``.
 
     ``state_dict`` maps the PEFT keys
-    ``base_model.model.model.layers.{i}.mlp.down_proj.lora_{A,B}.weight`` (an
-    adapter name between ``lora_A`` and ``weight``, as in ``lora_A.default.
-    weight``, is dropped) to arrays or tensors; ``adapter_config`` is the
-    parsed ``adapter_config.json`` (``r``, ``lora_alpha``, ``target_modules``).
-    The files are named as the reference's loader reads them
-    (``layers.{i}.mlp.down_proj.lora_A.weight``, peft_weight_allocator.cc:
-    171-240), raw ``tofile`` of the HF row-major tensor, and the config is
-    copied next to them as ``adapter_config.json`` (``Model.load_lora(folder)``
-    takes rank and alpha from it).  Only ``down_proj`` is served: any other
-    target module, in the config or among the keys, raises ``ValueError``.
-    Needs no ``peft`` package."""
+    ``base_model.model.model.layers.{i}.self_attn.{q,k,v,o}_proj.lora_{A,B}.weight``
+    and ``...layers.{i}.mlp.down_proj.lora_{A,B}.weight`` (an adapter name
+    between ``lora_A`` and ``weight``, as in ``lora_A.default.weight``, is
+    dropped) to arrays or tensors; ``adapter_config`` is the parsed
+    ``adapter_config.json`` (``r``, ``lora_alpha``, ``target_modules``).  The
+    files are named as the reference's loader reads them
+    (``layers.{i}.self_attn.q_proj.lora_A.weight``, ``layers.{i}.mlp.down_proj.
+    lora_A.weight``, peft_weight_allocator.cc:171-240), raw ``tofile`` of the
+    HF row-major tensor, and the config is copied next to them as
+    ``adapter_config.json`` (``Model.load_lora(folder)`` takes the target
+    modules, rank and alpha from it).  Served: any non-empty subset of
+    ``q_proj, k_proj, v_proj, o_proj, down_proj``.  ``ValueError``: another
+    target module (``gate_proj``, ``up_proj``, ...) or none, a target whose
+    tensors are missing or incomplete, a tensor of a module that is not a
+    target, ``rank_pattern`` / ``alpha_pattern`` (one rank and one alpha per
+    adapter).  Needs no ``peft`` package."""
     targets = adapter_config.get("target_modules") or []
     if isinstance(targets, str):
         targets = [targets]
-    bad = sorted(t for t in targets if t.split(".")[-1] != "down_proj")
+    targets = [t.split(".")[-1] for t in targets]
+    bad = sorted(t for t in targets if t not in _PEFT_SERVED)
     if bad or not targets:
-        raise ValueError(f"convert_peft_adapter: only down_proj adapters are served, got {targets}")
+        raise ValueError("convert_peft_adapter: adapters on q_proj, k_proj, v_proj, o_proj and "
+                         f"down_proj are served, got {targets}")
     if adapter_config.get("peft_type", "LORA") != "LORA":
         raise ValueError(f"convert_peft_adapter: peft_type {adapter_config.get('peft_type')}")
+    if adapter_config.get("rank_pattern") or adapter_config.get("alpha_pattern"):
+        raise ValueError("convert_peft_adapter: rank_pattern / alpha_pattern are not served")
     rank, alpha = int(adapter_config["r"]), float(adapter_config["lora_alpha"])
     tensors = {}
     for key, val in state_dict.items():
@@ -112,8 +124,9 @@ def convert_peft_adapter(state_dict: Mapping, adapter_config: Mapping, dst_folde
             continue
         name = key[len(_PEFT_PREFIX):] if key.startswith(_PEFT_PREFIX) else key
         parts = name.split(".")
-        # layers.{i}.mlp.down_proj.lora_A[.adapter].weight
-        if (len(parts) not in (6, 7) or parts[0] != "layers" or parts[2:4] != ["mlp", "down_proj"]
+        # layers.{i}.{self_attn,mlp}.{module}.lora_A[.adapter].weight
+        if (len(parts) not in (6, 7) or parts[0] != "layers" or parts[3] not in targets
+                or _PEFT_SERVED[parts[3]] != parts[2]
                 or parts[4] not in ("lora_A", "lora_B") or parts[-1] != "weight"):
             raise ValueError(f"convert_peft_adapter: cannot serve adapter tensor {key}")
         arr = val.detach().cpu().float().numpy() if hasattr(val, "detach") else np.asarray(val)
@@ -122,9 +135,11 @@ def convert_peft_adapter(state_dict: Mapping, adapter_config: Mapping, dst_folde
             raise ValueError(f"convert_peft_adapter: {key} has shape {arr.shape}, rank {rank}")
         tensors[".".join(parts[:5] + ["weight"])] = arr
     layers = {n.split(".")[1] for n in tensors}
-    if not tensors or any(f"layers.{i}.mlp.down_proj.lora_{ab}.weight" not in tensors
-                          for i in layers for ab in "AB"):
-        raise ValueError("convert_peft_adapter: lora_A / lora_B of down_proj missing")
+    missing = [f"layers.{i}.{_PEFT_SERVED[t]}.{t}.lora_{ab}.weight"
+               for t in sorted(set(targets)) for i in sorted(layers) for ab in "AB"
+               if f"layers.{i}.{_PEFT_SERVED[t]}.{t}.lora_{ab}.weight" not in tensors]
+    if not tensors or missing:
+        raise ValueError(f"convert_peft_adapter: lora_A / lora_B missing: {missing[:4]}")
     os.makedirs(dst_folder, exist_ok=True)
     for name, arr in tensors.items():
         np.ascontiguousarray(arr, dtype=dtype).tofile(os.path.join(dst_folder, name))

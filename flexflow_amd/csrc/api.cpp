@@ -737,6 +737,31 @@ extern "C" ffmi_status ffmi_lora_apply(const void *x, int T, int F, int H, const
   return FFMI_OK;
 }
 
+extern "C" size_t ffmi_lora_qkv_workspace_bytes(int T, int in_dim) {
+  return 3 * ffmi::lora_workspace_bytes(T, in_dim);
+}
+
+extern "C" ffmi_status ffmi_lora_apply_qkv(const void *x, int T, int in_dim, const int *seg_width,
+                                           const int32_t *slots,
+                                           const ffmi_lora_entry *const *table, void *y, int ldy,
+                                           int x_packed, void *ws, size_t ws_bytes, void *h_out,
+                                           ffmi_stream stream) {
+  FFMI_CHECK(x && seg_width && slots && table && y && T >= 0 && in_dim > 0, FFMI_ERR_INVALID);
+  FFMI_CHECK(in_dim % 32 == 0, FFMI_ERR_INVALID);
+  long sum = 0;
+  for (int g = 0; g < 3; ++g) {
+    FFMI_CHECK(table[g] && seg_width[g] > 0 && seg_width[g] % 8 == 0, FFMI_ERR_INVALID);
+    sum += seg_width[g];
+  }
+  FFMI_CHECK(ldy >= sum && sum < (1L << 30), FFMI_ERR_INVALID);
+  FFMI_CHECK(T == 0 || (ws && ws_bytes >= 3 * ffmi::lora_workspace_bytes(T, in_dim)),
+             FFMI_ERR_INVALID);
+  FFMI_HIP(ffmi::launch_lora_qkv((const uint16_t *)x, T, in_dim, seg_width, ldy, slots, table,
+                                 (uint16_t *)y, x_packed != 0, (float *)ws, (uint16_t *)h_out,
+                                 (hipStream_t)stream));
+  return FFMI_OK;
+}
+
 extern "C" uint32_t ffmi_sampling_counter(uint64_t seed, int64_t guid, int pos) {
   uint64_t x = seed ^ ((uint64_t)guid * 0x9e3779b97f4a7c15ull) ^
                ((uint64_t)(int64_t)pos * 0xd1342543de82ef95ull);

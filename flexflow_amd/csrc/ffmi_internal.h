@@ -270,6 +270,12 @@ size_t lora_workspace_bytes(int T, int F);
 hipError_t launch_lora(const uint16_t *x, int T, int F, int H, const int32_t *slots,
                        const ffmi_lora_entry *table, uint16_t *y, bool x_packed, float *ws,
                        uint16_t *h_out, hipStream_t s);
+// the qkv site: y [T][ldy] = [Q | K | V] of widths w[3], one table per segment,
+// ws 3 * lora_workspace_bytes(T, F), h_out NULL or [3][T][64] (ffmi_lora_apply_qkv)
+hipError_t launch_lora_qkv(const uint16_t *x, int T, int F, const int *w, int ldy,
+                           const int32_t *slots, const ffmi_lora_entry *const *tables,
+                           uint16_t *y, bool x_packed, float *ws, uint16_t *h_out,
+                           hipStream_t s);
 // Vocab-sharded tail (vshard_kernel): phase 0..2 write this rank's exchange
 // record ([P][T][W] floats, W >= max(4, 2k)); phase 3 merges into ids/probs.
 hipError_t launch_vshard(const uint16_t *logits, int T, int Vl, int P, int rank, int k,

@@ -53,6 +53,18 @@ extern "C" ffmi_status ffmi_model_lora_load_folder(ffmi_model *m, const char *fo
   return m->lora_load_folder(folder, rank, alpha, id_out);
 }
 
+extern "C" ffmi_status ffmi_model_lora_load_modules(ffmi_model *m, int rank, float alpha, int n,
+                                                    const ffmi_lora_module *mods, int *id_out) {
+  if (!m || !id_out || n < 0 || (n > 0 && !mods)) return FFMI_ERR_INVALID;
+  return m->lora_load_modules(rank, alpha, n, mods, id_out);
+}
+
+extern "C" ffmi_status ffmi_model_lora_load_folder_ex(ffmi_model *m, const char *folder, int rank,
+                                                      float alpha, unsigned modules, int *id_out) {
+  if (!m || !folder || !id_out) return FFMI_ERR_INVALID;
+  return m->lora_load_folder_ex(folder, rank, alpha, modules, id_out);
+}
+
 extern "C" ffmi_status ffmi_model_lora_unload(ffmi_model *m, int id) {
   if (!m) return FFMI_ERR_INVALID;
   return m->lora_unload(id);

@@ -178,84 +178,153 @@ struct LlamaGPU : public ffmi_model {
     step_targets.v.resize(bc.num_tokens);
     for (int t = 0; t < bc.num_tokens; ++t) step_targets.v[t] = bc.tokensInfo[t].score_id;
   }
-  // LoRA adapters on down_proj (FFMI_MODEL_LORA; lora_linear.cc): under the
-  // flag the down projection runs with its own reduce pass, outside the fused
-  // residual norms, and ffmi::launch_lora follows on proj.  Each row's adapter
-  // (BatchConfig::PerRequestInfo::lora_id of its request, -1 for an adapter
-  // this model did not load) rides the blob behind the records, the draws and
-  // the targets, so a replayed graph reads fresh assignments; a step none of
-  // whose rows has an adapter skips the launches (part of the graph key).
-  // Adapter storage and the device table [L][FFMI_LORA_MAX_ADAPTERS] are
-  // allocated at creation / load, never in a step.
+  // LoRA adapters (FFMI_MODEL_LORA; lora_linear.cc) on q / k / v / o and
+  // down_proj.  Each row's adapter (BatchConfig::PerRequestInfo::lora_id of
+  // its request, -1 for an adapter this model did not load) rides the blob
+  // behind the records, the draws and the targets, so a replayed graph reads
+  // fresh assignments.  The step's module mask -- the union of the modules of
+  // the adapters its rows name -- decides which sites leave their fused route
+  // and run the LoRA launches (enqueue), and is part of the graph key.  On a
+  // model that uses the fused residual norms, which are not bit-identical to
+  // the norm launches, the modules of every resident adapter with an
+  // attention module count too (lora_route), so that a row without an adapter
+  // has the same bits in every step.  Adapter storage and the device table
+  // [L][kLoraMods][FFMI_LORA_MAX_ADAPTERS] are allocated at creation / load,
+  // never in a step.
+  static constexpr int kLoraMods = 5;  // FFMI_LORA_Q .. FFMI_LORA_DOWN
+  static constexpr unsigned kLoraQKV = FFMI_LORA_Q_BIT | FFMI_LORA_K_BIT | FFMI_LORA_V_BIT;
   bool lora = false;
   ffmi_lora_entry *lora_tab = nullptr;
   std::vector<ffmi_lora_entry> lora_tab_h;
-  uint16_t *lora_A[FFMI_LORA_MAX_ADAPTERS] = {}, *lora_B[FFMI_LORA_MAX_ADAPTERS] = {};
+  uint16_t *lora_A[kLoraMods][FFMI_LORA_MAX_ADAPTERS] = {}, *lora_B[kLoraMods][FFMI_LORA_MAX_ADAPTERS] = {};
+  unsigned lora_mods[FFMI_LORA_MAX_ADAPTERS] = {};  // modules of each loaded adapter (0: not loaded)
   float *lora_ws = nullptr;
   StepExtra<int32_t> step_slots;
-  bool step_lora_any = false;
+  unsigned step_lora_mask = 0;
+  size_t lora_tab_at(int l, int mod, int id) const {
+    return ((size_t)l * kLoraMods + mod) * FFMI_LORA_MAX_ADAPTERS + id;
+  }
+  // (the step-independent part of enqueue's `fuse`: can any step of this model
+  // take the fused residual norms?)
+  bool lora_fuse_capable() const {
+    return (fuse_norms == 2 || (fuse_norms == 1 && c.hidden >= 2048)) && o.tp_size == 1 &&
+           c.hidden % 32 == 0 && Hl % 32 == 0 && c.hidden <= 4096;
+  }
   void take_step_slots(const BatchConfig &bc) {
     step_slots.v.resize(bc.num_tokens);
-    step_lora_any = false;
+    step_lora_mask = 0;
     for (int t = 0; t < bc.num_tokens; ++t) {
       const int a = bc.requestsInfo[bc.tokensInfo[t].request_index].lora_id;
-      step_slots.v[t] = a >= 0 && a < FFMI_LORA_MAX_ADAPTERS && lora_A[a] ? a : -1;
-      step_lora_any = step_lora_any || step_slots.v[t] >= 0;
+      step_slots.v[t] = a >= 0 && a < FFMI_LORA_MAX_ADAPTERS && lora_mods[a] ? a : -1;
+      if (step_slots.v[t] >= 0) step_lora_mask |= lora_mods[a];
     }
+  }
+  // the modules whose route this step takes
+  unsigned lora_route() const {
+    if (!lora) return 0;
+    unsigned m = step_lora_mask;
+    // (a down-only adapter keeps the per-step route it has always had: a step
+    // that names none is the fused step, launch for launch)
+    if (lora_fuse_capable())
+      for (int a = 0; a < FFMI_LORA_MAX_ADAPTERS; ++a)
+        if (lora_mods[a] & ~FFMI_LORA_DOWN_BIT) m |= lora_mods[a];
+    return m;
   }
   static ffmi_status refuse(const char *why) {
     ffmi_set_last_error(why, __FILE__, __LINE__);
     return FFMI_ERR_UNSUPPORTED;
   }
+  static ffmi_status invalid(const char *why) {
+    ffmi_set_last_error(why, __FILE__, __LINE__);
+    return FFMI_ERR_INVALID;
+  }
+  // a module's dimensions: the HF tensor's (in, out) and the device's out
+  // (k / v under the replicated load: every query head its K/V head's rows)
+  void lora_dims(int mod, int *in, int *out_hf, int *out_dev) const {
+    const int H = c.hidden;
+    *in = mod == FFMI_LORA_DOWN ? Fl : H;
+    const bool kv = mod == FFMI_LORA_K || mod == FFMI_LORA_V;
+    *out_hf = kv ? c.num_kv_heads * d : H;
+    *out_dev = kv ? Hkv : mod == FFMI_LORA_Q ? Hl : H;
+  }
   ffmi_status lora_load(int rank, float alpha, const void *A, const void *B, int *id_out) override {
     if (!lora) return ffmi_model::lora_load(rank, alpha, A, B, id_out);
     FFMI_CHECK(A && B && id_out && rank >= 1 && std::isfinite(alpha), FFMI_ERR_INVALID);
+    const ffmi_lora_module m{FFMI_LORA_DOWN, A, B};
+    return lora_load_modules(rank, alpha, 1, &m, id_out);
+  }
+  ffmi_status lora_load_modules(int rank, float alpha, int n, const ffmi_lora_module *mods,
+                                int *id_out) override {
+    if (!lora) return ffmi_model::lora_load_modules(rank, alpha, n, mods, id_out);
+    if (n <= 0 || !mods) return invalid("lora: an adapter without modules");
+    unsigned seen = 0;
+    for (int i = 0; i < n; ++i) {
+      const int mod = mods[i].module;
+      if (mod == FFMI_LORA_GATE || mod == FFMI_LORA_UP)
+        return refuse("lora: gate_proj / up_proj adapters are not served");
+      if (mod < 0 || mod >= kLoraMods) return invalid("lora: unknown module");
+      if ((seen >> mod) & 1u) return invalid("lora: a module listed twice");
+      seen |= 1u << mod;
+    }
+    FFMI_CHECK(id_out && rank >= 1 && std::isfinite(alpha), FFMI_ERR_INVALID);
+    for (int i = 0; i < n; ++i) FFMI_CHECK(mods[i].A && mods[i].B, FFMI_ERR_INVALID);
     if (rank > FFMI_LORA_MAX_RANK) return refuse("lora: rank above FFMI_LORA_MAX_RANK");
-    const int L = c.num_layers, F = Fl, H = c.hidden, R = FFMI_LORA_MAX_RANK;
-    // A as the packed activation tiles of a [R][F] matrix (one MFMA operand
-    // fragment per 16 ranks x 32 columns), B [H][R]; zero beyond the rank
-    const uint16_t *a = static_cast<const uint16_t *>(A), *b = static_cast<const uint16_t *>(B);
-    std::vector<uint16_t> ap((size_t)L * R * F, 0), bp((size_t)L * H * R, 0);
-    for (int l = 0; l < L; ++l) {
-      for (int j = 0; j < rank; ++j)
-        for (int k = 0; k < F; ++k)
-          ap[(size_t)l * R * F + act_packed_off(j, k, F)] = a[((size_t)l * rank + j) * F + k];
-      for (int n = 0; n < H; ++n)
-        memcpy(&bp[((size_t)l * H + n) * R], &b[((size_t)l * H + n) * rank], (size_t)rank * 2);
-    }
-    uint16_t *ad = nullptr, *bd = nullptr;
-    if (hipMalloc((void **)&ad, ap.size() * 2) != hipSuccess ||
-        hipMalloc((void **)&bd, bp.size() * 2) != hipSuccess) {
-      (void)hipFree(ad);
-      (void)hipGetLastError();
-      ffmi_set_last_error("lora: adapter alloc", __FILE__, __LINE__);
-      return FFMI_ERR_OOM;
-    }
+    const int L = c.num_layers, R = FFMI_LORA_MAX_RANK;
     const int id = lora_id_acquire(this);
     if (id < 0) {
-      (void)hipFree(ad), (void)hipFree(bd);
       ffmi_set_last_error("lora: FFMI_LORA_MAX_ADAPTERS adapters are loaded", __FILE__, __LINE__);
       return FFMI_ERR_OOM;
     }
     const _Float16 s16 = (_Float16)(alpha / (float)rank);
-    for (int l = 0; l < L; ++l) {
-      ffmi_lora_entry &e = lora_tab_h[(size_t)l * FFMI_LORA_MAX_ADAPTERS + id];
-      e.A = ad + (size_t)l * R * F, e.B = bd + (size_t)l * H * R;
-      e.scale = (float)s16, e.rank = rank;
-    }
-    // (blocking copies; steps in flight read the table's other entries only)
     const hipError_t e0 = hipStreamSynchronize(stream);
-    const hipError_t e1 = hipMemcpy(ad, ap.data(), ap.size() * 2, hipMemcpyHostToDevice);
-    const hipError_t e2 = hipMemcpy(bd, bp.data(), bp.size() * 2, hipMemcpyHostToDevice);
-    const hipError_t e3 = hipMemcpy(lora_tab, lora_tab_h.data(),
-                                    lora_tab_h.size() * sizeof(ffmi_lora_entry),
-                                    hipMemcpyHostToDevice);
-    lora_A[id] = ad, lora_B[id] = bd;
-    if (e0 != hipSuccess || e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) {
-      (void)lora_unload(id);
-      ffmi_set_last_error("lora: adapter upload", __FILE__, __LINE__);
-      return FFMI_ERR_HIP;
+    bool oom = false, bad = e0 != hipSuccess;
+    for (int i = 0; i < n && !oom && !bad; ++i) {
+      const int mod = mods[i].module;
+      int F, No, N;
+      lora_dims(mod, &F, &No, &N);
+      // A as the packed activation tiles of a [R][F] matrix (one MFMA operand
+      // fragment per 16 ranks x 32 columns), B [N][R]; zero beyond the rank
+      const uint16_t *a = static_cast<const uint16_t *>(mods[i].A);
+      const uint16_t *b = static_cast<const uint16_t *>(mods[i].B);
+      const int G = N / No;  // (> 1: k / v rows replicated to the query heads)
+      std::vector<uint16_t> ap((size_t)L * R * F, 0), bp((size_t)L * N * R, 0);
+      for (int l = 0; l < L; ++l) {
+        for (int j = 0; j < rank; ++j)
+          for (int k = 0; k < F; ++k)
+            ap[(size_t)l * R * F + act_packed_off(j, k, F)] = a[((size_t)l * rank + j) * F + k];
+        for (int r = 0; r < N; ++r) {
+          const int src = G > 1 ? (r / d / G) * d + r % d : r;
+          memcpy(&bp[((size_t)l * N + r) * R], &b[((size_t)l * No + src) * rank], (size_t)rank * 2);
+        }
+      }
+      uint16_t *ad = nullptr, *bd = nullptr;
+      if (hipMalloc((void **)&ad, ap.size() * 2) != hipSuccess ||
+          hipMalloc((void **)&bd, bp.size() * 2) != hipSuccess) {
+        (void)hipFree(ad);
+        (void)hipGetLastError();
+        oom = true;
+        break;
+      }
+      lora_A[mod][id] = ad, lora_B[mod][id] = bd;
+      for (int l = 0; l < L; ++l) {
+        ffmi_lora_entry &e = lora_tab_h[lora_tab_at(l, mod, id)];
+        e.A = ad + (size_t)l * R * F, e.B = bd + (size_t)l * N * R;
+        e.scale = (float)s16, e.rank = rank;
+      }
+      // (blocking copies; steps in flight read the table's other entries only)
+      bad = hipMemcpy(ad, ap.data(), ap.size() * 2, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(bd, bp.data(), bp.size() * 2, hipMemcpyHostToDevice) != hipSuccess;
     }
+    if (!oom && !bad)
+      bad = hipMemcpy(lora_tab, lora_tab_h.data(), lora_tab_h.size() * sizeof(ffmi_lora_entry),
+                      hipMemcpyHostToDevice) != hipSuccess;
+    if (oom || bad) {
+      (void)hipGetLastError();
+      (void)lora_unload(id);
+      ffmi_set_last_error(oom ? "lora: adapter alloc" : "lora: adapter upload", __FILE__, __LINE__);
+      return oom ? FFMI_ERR_OOM : FFMI_ERR_HIP;
+    }
+    lora_mods[id] = seen;
     *id_out = id;
     return FFMI_OK;
   }
@@ -263,30 +332,70 @@ struct LlamaGPU : public ffmi_model {
   ffmi_status lora_read(const std::string &path, size_t n, uint16_t *dst) {
     return tensor_status(read_tensor(path, n, dst), "lora: adapter file", path);
   }
+  // (the older entry point keeps tensor_status's own code for a missing or
+  // wrong-sized file; _ex answers FFMI_ERR_UNSUPPORTED, as its contract says)
   ffmi_status lora_load_folder(const char *folder, int rank, float alpha, int *id_out) override {
     if (!lora) return ffmi_model::lora_load_folder(folder, rank, alpha, id_out);
+    return lora_load_files(folder, rank, alpha, FFMI_LORA_DOWN_BIT, id_out, false);
+  }
+  ffmi_status lora_load_folder_ex(const char *folder, int rank, float alpha, unsigned modules,
+                                  int *id_out) override {
+    if (!lora) return ffmi_model::lora_load_folder_ex(folder, rank, alpha, modules, id_out);
+    return lora_load_files(folder, rank, alpha, modules, id_out, true);
+  }
+  ffmi_status lora_load_files(const char *folder, int rank, float alpha, unsigned modules,
+                              int *id_out, bool file_unsupported) {
     FFMI_CHECK(rank >= 1, FFMI_ERR_INVALID);
     if (rank > FFMI_LORA_MAX_RANK) return refuse("lora: rank above FFMI_LORA_MAX_RANK");
-    // only down_proj is served: an adapter tensor of any other module refuses
+    if (modules & ((1u << FFMI_LORA_GATE) | (1u << FFMI_LORA_UP)))
+      return refuse("lora: gate_proj / up_proj adapters are not served");
+    if (!modules || (modules >> kLoraMods)) return invalid("lora: no module, or an unknown one, in the mask");
+    static const char *const names[kLoraMods] = {".self_attn.q_proj.lora_", ".self_attn.k_proj.lora_",
+                                                 ".self_attn.v_proj.lora_", ".self_attn.o_proj.lora_",
+                                                 ".mlp.down_proj.lora_"};
+    // an adapter tensor of a module outside the mask (gate / up included) refuses
     if (DIR *dir = opendir(folder)) {
       bool other = false;
       while (const dirent *de = readdir(dir)) {
         const std::string n = de->d_name;
-        if (n.find(".lora_") != std::string::npos && n.find(".mlp.down_proj.lora_") == std::string::npos)
-          other = true;
+        if (n.find(".lora_") == std::string::npos) continue;
+        bool mine = false;
+        for (int mod = 0; mod < kLoraMods; ++mod)
+          mine = mine || (((modules >> mod) & 1u) && n.find(names[mod]) != std::string::npos);
+        other = other || !mine;
       }
       closedir(dir);
-      if (other) return refuse("lora: the adapter targets a module other than down_proj");
+      if (other) return refuse("lora: the folder holds an adapter tensor of a module that was not asked for");
     }
-    const int L = c.num_layers, F = c.intermediate, H = c.hidden;
-    std::vector<uint16_t> a((size_t)L * rank * F), b((size_t)L * H * rank);
-    for (int l = 0; l < L; ++l) {
-      const std::string p = std::string(folder) + "/layers." + std::to_string(l) + ".mlp.down_proj.lora_";
-      ffmi_status st = lora_read(p + "A.weight", (size_t)rank * F, &a[(size_t)l * rank * F]);
-      if (st == FFMI_OK) st = lora_read(p + "B.weight", (size_t)H * rank, &b[(size_t)l * H * rank]);
-      if (st != FFMI_OK) return st;
+    const int L = c.num_layers;
+    std::vector<std::vector<uint16_t>> as, bs;
+    std::vector<ffmi_lora_module> mods;
+    for (int mod = 0; mod < kLoraMods; ++mod) {
+      if (!((modules >> mod) & 1u)) continue;
+      int F, No, N;
+      lora_dims(mod, &F, &No, &N);
+      // (the files hold the unsharded HF tensors; tp_size is 1 under the flag)
+      as.emplace_back((size_t)L * rank * F), bs.emplace_back((size_t)L * No * rank);
+      for (int l = 0; l < L; ++l) {
+        const std::string p = std::string(folder) + "/layers." + std::to_string(l) + names[mod];
+        ffmi_status st = lora_read(p + "A.weight", (size_t)rank * F, &as.back()[(size_t)l * rank * F]);
+        if (st == FFMI_OK) st = lora_read(p + "B.weight", (size_t)No * rank, &bs.back()[(size_t)l * No * rank]);
+        if (st != FFMI_OK) return file_unsupported ? FFMI_ERR_UNSUPPORTED : st;
+      }
     }
-    return lora_load(rank, alpha, a.data(), b.data(), id_out);
+    for (int mod = 0, i = 0; mod < kLoraMods; ++mod)
+      if ((modules >> mod) & 1u) {
+        mods.push_back(ffmi_lora_module{mod, as[i].data(), bs[i].data()});
+        ++i;
+      }
+    return lora_load_modules(rank, alpha, (int)mods.size(), mods.data(), id_out);
+  }
+  void lora_free(int id) {
+    for (int mod = 0; mod < kLoraMods; ++mod) {
+      (void)hipFree(lora_A[mod][id]), (void)hipFree(lora_B[mod][id]);
+      lora_A[mod][id] = lora_B[mod][id] = nullptr;
+    }
+    lora_mods[id] = 0;
   }
   ffmi_status lora_unload(int id) override {
     if (!lora) return ffmi_model::lora_unload(id);
@@ -297,12 +406,13 @@ struct LlamaGPU : public ffmi_model {
     }
     // no step reads the entries any more: clear them, then free the storage
     for (int l = 0; l < c.num_layers; ++l)
-      lora_tab_h[(size_t)l * FFMI_LORA_MAX_ADAPTERS + id] = ffmi_lora_entry{};
-    FFMI_HIP(hipStreamSynchronize(stream));
-    FFMI_HIP(hipMemcpy(lora_tab, lora_tab_h.data(), lora_tab_h.size() * sizeof(ffmi_lora_entry),
-                       hipMemcpyHostToDevice));
-    (void)hipFree(lora_A[id]), (void)hipFree(lora_B[id]);
-    lora_A[id] = lora_B[id] = nullptr;
+      for (int mod = 0; mod < kLoraMods; ++mod) lora_tab_h[lora_tab_at(l, mod, id)] = ffmi_lora_entry{};
+    const hipError_t e0 = hipStreamSynchronize(stream);
+    const hipError_t e1 = hipMemcpy(lora_tab, lora_tab_h.data(),
+                                    lora_tab_h.size() * sizeof(ffmi_lora_entry), hipMemcpyHostToDevice);
+    lora_free(id);
+    FFMI_HIP(e0);
+    FFMI_HIP(e1);
     return FFMI_OK;
   }
   // vocab-sharded lm_head at TP > 1 (model.cc:3392-3419): this rank's Vl rows
@@ -682,7 +792,7 @@ struct LlamaGPU : public ffmi_model {
     if (chain_t0) (void)hipEventDestroy(chain_t0);
     clear_graphs();
     lora_id_release_all(this);
-    for (int i = 0; i < FFMI_LORA_MAX_ADAPTERS; ++i) (void)hipFree(lora_A[i]), (void)hipFree(lora_B[i]);
+    for (int i = 0; i < FFMI_LORA_MAX_ADAPTERS; ++i) lora_free(i);
     for (auto &L : layers) ffmi_attn_destroy(L.attn);
     for (auto e : ev_pool) (void)hipEventDestroy(e);
     for (auto e : ev_chunk) (void)hipEventDestroy(e);
@@ -768,10 +878,12 @@ struct LlamaGPU : public ffmi_model {
     ss_d = ss_o + (size_t)32 * (H / 16);
     TRY(alloc(&mlp, (size_t)Tm * Fl));
     if (lora) {
-      lora_tab_h.assign((size_t)c.num_layers * FFMI_LORA_MAX_ADAPTERS, ffmi_lora_entry{});
+      lora_tab_h.assign((size_t)c.num_layers * kLoraMods * FFMI_LORA_MAX_ADAPTERS, ffmi_lora_entry{});
       TRY(alloc(&lora_tab, lora_tab_h.size()));
       FFMI_HIP(hipMemset(lora_tab, 0, lora_tab_h.size() * sizeof(ffmi_lora_entry)));
-      TRY(alloc(&lora_ws, (ffmi::lora_workspace_bytes(Tm, Fl) + 3) / 4));
+      // (the largest site: down, o, or the three segments of qkv)
+      TRY(alloc(&lora_ws, (std::max({ffmi::lora_workspace_bytes(Tm, Fl), ffmi::lora_workspace_bytes(Tm, Hl),
+                                     3 * ffmi::lora_workspace_bytes(Tm, H)}) + 3) / 4));
     }
     // (a GQA handle does not fold the o projection in: the GEMM runs)
     fuse_ao = !native_gqa && P == 1 && d == 64 && H <= 1024 && H % 16 == 0 &&
@@ -1077,11 +1189,11 @@ struct LlamaGPU : public ffmi_model {
   struct GraphKey {
     int T, W, C, k, parity, overlap, fused, max_q, slot;
     size_t bytes;
-    int lora_any = 0;  // (FFMI_MODEL_LORA: a row of the step has an adapter)
+    int lora_mask = 0;  // (FFMI_MODEL_LORA: the modules whose route the step takes, lora_route)
     bool operator<(const GraphKey &o) const {
-      return std::tie(T, W, C, k, parity, overlap, fused, max_q, slot, bytes, lora_any) <
+      return std::tie(T, W, C, k, parity, overlap, fused, max_q, slot, bytes, lora_mask) <
              std::tie(o.T, o.W, o.C, o.k, o.parity, o.overlap, o.fused, o.max_q, o.slot, o.bytes,
-                      o.lora_any);
+                      o.lora_mask);
     }
   };
   // TREE steps write alternate halves of the attention staging (commits of
@@ -1144,7 +1256,7 @@ struct LlamaGPU : public ffmi_model {
   // adapter ids, in that order.  A BEAM step never has any: set_sampling and
   // set_logprobs refuse a BEAM model and creation refuses FFMI_MODEL_LORA on
   // one, so a chained or grouped slot's blob is its records alone and its key
-  // has lora_any = 0.  *key is set for a step with rows only.
+  // has lora_mask = 0.  *key is set for a step with rows only.
   ffmi_status stage_step(int k, int slot, Step *s, GraphKey *key) {
     const int T = (int)ps.tokens.size();
     ffmi_batch_dev *b = chain_batch[slot];
@@ -1169,7 +1281,7 @@ struct LlamaGPU : public ffmi_model {
     s->blob_bytes = bytes;
     *key = GraphKey{T, b->num_work, b->num_commits, k, tree_parity, b->commit_overlap ? 1 : 0,
                     (b->one_item_per_req ? 1 : 0) | (b->lds_tail ? 2 : 0), b->max_q, slot, bytes,
-                    lora && step_lora_any ? 1 : 0};
+                    (int)lora_route()};
     return FFMI_OK;
   }
 
@@ -1302,13 +1414,22 @@ struct LlamaGPU : public ffmi_model {
     int mark_i = 0;
     const bool fuse = (fuse_norms == 2 || (fuse_norms == 1 && H >= 2048)) && !dbg &&
                       o.tp_size == 1 && T <= 32 && H % 32 == 0 && Hl % 32 == 0 && H <= 4096;
-    // (FFMI_MODEL_LORA, a step with an adapter on some row: down runs unfused
-    // and its split-K slabs are reduced into proj for the update, so the norm
-    // after it -- the next layer's attention norm, the final norm -- is a
-    // launch again; o and gate/up keep their fused pair.  A step without
-    // adapters is the step of a model without the flag)
-    const bool lora_step = lora && step_lora_any;
-    const bool fuse_d = fuse && !lora_step;
+    // (FFMI_MODEL_LORA, the modules of the step's route, lora_route.  down: it
+    // runs unfused and its split-K slabs are reduced into proj for the update,
+    // so the norm after it -- the next layer's attention norm, the final norm
+    // -- is a launch again.  o: the same for the o projection and the
+    // post-attention norm, and gate/up then reads the norm's output; an o
+    // projection folded into the attention stays there, its per-head slabs
+    // reduced into proj.  q / k / v: the attention norm is a launch, the qkv
+    // GEMM writes reduced fp16 rows and the update runs on them before the
+    // attention.  A step with an empty route is the step of a model without
+    // the flag)
+    const unsigned lroute = lora_route();
+    const bool lora_step = (lroute & FFMI_LORA_DOWN_BIT) != 0, lora_o = (lroute & FFMI_LORA_O_BIT) != 0,
+               lora_qkv = (lroute & kLoraQKV) != 0;
+    const bool fuse_d = fuse && !lora_step, fuse_o = fuse && !lora_o;
+    const int32_t *const lslots =
+        lora ? reinterpret_cast<const int32_t *>(step.batch->dev + step_slots.off) : nullptr;
     // the residual norms inside the transport's all-reduces (tp_fuse_norm)
     const bool arn = peer && !solo && o.tp_size > 1 && (tp_fuse_norm == 2 || (tp_fuse_norm == 1 && !dbg));
     for (int l = 0; l < c.num_layers; ++l) {
@@ -1329,7 +1450,7 @@ struct LlamaGPU : public ffmi_model {
       // fused residual norms (see fuse_norms): from layer 1 on, the attention
       // norm is the qkv GEMM's prologue on the residual the down projection
       // left, and every post-attention norm the gate/up GEMM's
-      const bool fz_in = fuse_d && l > 0;
+      const bool fz_in = fuse_d && l > 0 && !lora_qkv;
       ffmi::FuseArgs fz_qkv, fz_o, fz_gu, fz_d;
       if (fuse) {
         fz_o.kind = fz_d.kind = 1;
@@ -1341,7 +1462,12 @@ struct LlamaGPU : public ffmi_model {
         fz_qkv.wnorm = L.in_norm, fz_gu.wnorm = L.post_norm;
         fz_qkv.eps = fz_gu.eps = eps;
       }
-      if (!fz_in && !(arn && l > 0)) {  // (arn: the previous down all-reduce normalised)
+      if (fuse_d && l > 0 && lora_qkv) {  // (res holds the residual add: the norm alone)
+        pr = prof_begin(on);
+        FFMI_HIP(ffmi::launch_rmsnorm(res, nullptr, L.in_norm, nullptr, h, T, H, eps, stream, packed));
+        prof_end(pr, NORM, (double)T * H * 2 * 2, 0);
+        mk();
+      } else if (!fz_in && !(arn && l > 0)) {  // (arn: the previous down all-reduce normalised)
         pr = prof_begin(on);
         // layer 0: the embedding lookup gathers straight into the first norm
         // (embedding_kernels.cu:233-244; res = the looked-up rows)
@@ -1366,14 +1492,24 @@ struct LlamaGPU : public ffmi_model {
       ffmi::Partials qkv_part;
       // (a GQA handle takes fp16 qkv rows: a split-K plan runs its reduce pass)
       FFMI_HIP(ffmi::launch_gemm(fz_in ? res : h, L.wqkv, qkv, (float *)ws, ws_bytes, T, Nqkv, H,
-                                 fz_in ? wstream : XP, stream, native_gqa ? nullptr : &qkv_part, 0,
+                                 fz_in ? wstream : XP, stream,
+                                 native_gqa || lora_qkv ? nullptr : &qkv_part, 0,
                                  fz_in ? &fz_qkv : nullptr));
       prof_end(pr, GEMM_QKV, gemm_bytes(T, Nqkv, Nqkv, H), 2.0 * T * Nqkv * H);
+      if (lora_qkv) {  // qkv += scale * (h A^T) B^T per segment, ahead of RoPE and the KV store
+        pr = prof_begin(on);
+        const int w[3] = {Hl, Hkv, Hkv};
+        const ffmi_lora_entry *tabs[3];
+        for (int g = 0; g < 3; ++g) tabs[g] = lora_tab + lora_tab_at(l, g, 0);
+        FFMI_HIP(ffmi::launch_lora_qkv(h, T, H, w, Nqkv, lslots, tabs, qkv, packed, lora_ws, nullptr,
+                                       stream));
+        prof_end(pr, LORA, 2.0 * FFMI_LORA_MAX_RANK * (3.0 * H + Nqkv) + 4.0 * T * Nqkv, 0);
+      }
       mk();
       if (dbg) TRY(dbg_gemm_out(FFMI_DBG_QKV, l, qkv, qkv_part, T));
       pr = prof_begin(on);
       ffmi::OprojArgs oa;
-      if (fuse_ao && !fuse) {
+      if (fuse_ao && !fuse_o) {
         oa.wo = L.wo, oa.slab = oslab, oa.N = H, oa.max_T = oslab_T;
         oa.wts = ffmi::w_tile_stride(Hl / 32), oa.wks = ffmi::w_k_stride(H / 16);
       }
@@ -1386,7 +1522,7 @@ struct LlamaGPU : public ffmi_model {
       ffmi::Partials o_part;
       if (oa.done) {  // the attention projected: one slab per head
         o_part.p = oslab, o_part.S = heads_l, o_part.NP = H;
-      } else if (fuse) {  // o projection + residual add (+ sums of squares): res in place
+      } else if (fuse_o) {  // o projection + residual add (+ sums of squares): res in place
         pr = prof_begin(on);
         FFMI_HIP(ffmi::launch_gemm(att, L.wo, res, (float *)ws, ws_bytes, T, H, Hl, XP, stream,
                                    nullptr, 0, &fz_o));
@@ -1407,8 +1543,21 @@ struct LlamaGPU : public ffmi_model {
         prof_end(pr, ALLREDUCE, gemm_bytes(T, H, H, Hl), 2.0 * T * H * Hl);
         mk();
       }
+      if (lora_o) {  // proj += scale * (att A^T) B^T on the rows with an o adapter
+        pr = prof_begin(on);
+        // (split-K or per-head slabs summed in order and rounded once: the
+        // fp16 value the residual norm computes from them)
+        if (o_part.S > 0) {
+          FFMI_HIP(ffmi::launch_partials_reduce(o_part, proj, T, H, stream));
+          o_part = ffmi::Partials();
+        }
+        FFMI_HIP(ffmi::launch_lora(att, T, Hl, H, lslots, lora_tab + lora_tab_at(l, FFMI_LORA_O, 0),
+                                   proj, packed, lora_ws, nullptr, stream));
+        prof_end(pr, LORA, 2.0 * FFMI_LORA_MAX_RANK * ((double)Hl + H) + 4.0 * T * H, 0);
+        mk();
+      }
       if (dbg && !arn) TRY(dbg_gemm_out(FFMI_DBG_O_PROJ, l, proj, o_part, T));
-      if (!fuse && !arn) {
+      if (!fuse_o && !arn) {
         pr = prof_begin(on);
         FFMI_HIP(ffmi::launch_rmsnorm(res, proj, L.post_norm, res, h, T, H, eps, stream, packed,
                                       o_part));
@@ -1418,7 +1567,7 @@ struct LlamaGPU : public ffmi_model {
       if (dbg) TRY(dbg_copy(FFMI_DBG_FFN_NORM, l, h, T));
       pr = prof_begin(on);
       const int YP = packed ? FFMI_Y_PACKED : 0;
-      if (fuse)
+      if (fuse_o)
         FFMI_HIP(ffmi::launch_gemm(res, L.wgu, mlp, (float *)ws, ws_bytes, T, Fl, H,
                                    FFMI_EPI_SILU_MUL | YP | wstream, stream, nullptr, 0, &fz_gu));
       else
@@ -1447,9 +1596,8 @@ struct LlamaGPU : public ffmi_model {
             FFMI_HIP(ffmi::launch_partials_reduce(down_part, proj, T, H, stream));
             down_part = ffmi::Partials();
           }
-          FFMI_HIP(ffmi::launch_lora(mlp, T, Fl, H,
-                                     reinterpret_cast<const int32_t *>(batch->dev + step_slots.off),
-                                     lora_tab + (size_t)l * FFMI_LORA_MAX_ADAPTERS, proj, packed,
+          FFMI_HIP(ffmi::launch_lora(mlp, T, Fl, H, lslots,
+                                     lora_tab + lora_tab_at(l, FFMI_LORA_DOWN, 0), proj, packed,
                                      lora_ws, nullptr, stream));
           prof_end(pr, LORA, 2.0 * FFMI_LORA_MAX_RANK * ((double)Fl + H) + 4.0 * T * H, 0);
         }

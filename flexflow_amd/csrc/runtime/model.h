@@ -160,6 +160,23 @@ struct ffmi_model {
     ffmi_set_last_error("lora: the model was not created with FFMI_MODEL_LORA", __FILE__, __LINE__);
     return FFMI_ERR_UNSUPPORTED;
   }
+  // several modules of one adapter (ffmi_model_lora_load_modules /
+  // _load_folder_ex; FFMI_LORA_Q .. FFMI_LORA_DOWN)
+  virtual ffmi_status lora_load_modules(int rank, float alpha, int n, const ffmi_lora_module *mods,
+                                        int *id_out) {
+    // (down_proj alone is what lora_load takes: a model that serves that serves this)
+    if (n == 1 && mods && mods[0].module == FFMI_LORA_DOWN)
+      return lora_load(rank, alpha, mods[0].A, mods[0].B, id_out);
+    (void)rank, (void)alpha, (void)n, (void)mods, (void)id_out;
+    ffmi_set_last_error("lora: the model serves no adapters on these modules", __FILE__, __LINE__);
+    return FFMI_ERR_UNSUPPORTED;
+  }
+  virtual ffmi_status lora_load_folder_ex(const char *folder, int rank, float alpha,
+                                          unsigned modules, int *id_out) {
+    (void)folder, (void)rank, (void)alpha, (void)modules, (void)id_out;
+    ffmi_set_last_error("lora: the model was not created with FFMI_MODEL_LORA", __FILE__, __LINE__);
+    return FFMI_ERR_UNSUPPORTED;
+  }
   virtual ffmi_status lora_unload(int id) {
     (void)id;
     ffmi_set_last_error("lora: the model was not created with FFMI_MODEL_LORA", __FILE__, __LINE__);

@@ -39,6 +39,10 @@ SPEC_EXT_WIDTH4, SPEC_EXT_MULTI_SSM = 1, 2
 MODEL_NATIVE_GQA = 1
 MODEL_LORA = 4  # (2 is left unassigned: it stays an invalid flag)
 LORA_MAX_ADAPTERS, LORA_MAX_RANK = 8, 64
+# FFMI_LORA_Q .. FFMI_LORA_DOWN by the HF module name (masks: 1 << id); gate_proj
+# and up_proj have ids only so that the library can refuse them
+LORA_MODULES = {"q_proj": 0, "k_proj": 1, "v_proj": 2, "o_proj": 3, "down_proj": 4,
+                "gate_proj": 5, "up_proj": 6}
 # ffmi_attn_set_gqa_route
 GQA_ROUTE_AUTO, GQA_ROUTE_KV_INDEXED, GQA_ROUTE_GROUP_SHARED = 0, 1, 2
 ATTN_QTILE = 32
@@ -104,6 +108,11 @@ class ModelOpts(ctypes.Structure):
 class LoraEntry(ctypes.Structure):
     """ffmi_lora_entry: one adapter of ffmi_lora_apply's table."""
     _fields_ = [("A", c_void_p), ("B", c_void_p), ("scale", c_float), ("rank", c_int)]
+
+
+class LoraModule(ctypes.Structure):
+    """ffmi_lora_module: one module of ffmi_model_lora_load_modules."""
+    _fields_ = [("module", c_int), ("A", c_void_p), ("B", c_void_p)]
 
 
 class RMConfig(ctypes.Structure):
@@ -207,6 +216,14 @@ SIGNATURES = {
     "ffmi_model_lora_load_folder": (c_int, [c_void_p, ctypes.c_char_p, c_int, c_float,
                                             ctypes.POINTER(c_int)]),
     "ffmi_model_lora_unload": (c_int, [c_void_p, c_int]),
+    "ffmi_model_lora_load_modules": (c_int, [c_void_p, c_int, c_float, c_int,
+                                             ctypes.POINTER(LoraModule), ctypes.POINTER(c_int)]),
+    "ffmi_model_lora_load_folder_ex": (c_int, [c_void_p, ctypes.c_char_p, c_int, c_float,
+                                               ctypes.c_uint, ctypes.POINTER(c_int)]),
+    "ffmi_lora_qkv_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "ffmi_lora_apply_qkv": (c_int, [c_void_p, c_int, c_int, ctypes.POINTER(c_int), c_void_p,
+                                    ctypes.POINTER(c_void_p), c_void_p, c_int, c_int, c_void_p,
+                                    c_size_t, c_void_p, c_void_p]),
     "ffmi_lora_workspace_bytes": (c_size_t, [c_int, c_int]),
     "ffmi_lora_apply": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
                                 c_void_p, c_size_t, c_void_p, c_void_p]),

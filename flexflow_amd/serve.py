@@ -47,8 +47,8 @@ class Model:
         and the KV cache at num_kv_heads instead of replicated to every query
         head (FFMI_MODEL_NATIVE_GQA; fp16, num_kv_heads % tp_size == 0).
         logprobs: see set_logprobs.  lora: the model serves LoRA adapters on
-        down_proj (FFMI_MODEL_LORA; see load_lora): fp16 "inc" / "tree" models
-        at tp_size 1."""
+        q_proj / k_proj / v_proj / o_proj and down_proj (FFMI_MODEL_LORA; see
+        load_lora): fp16 "inc" / "tree" models at tp_size 1."""
         L = F.lib()
         self.config = dict(config)
         self.mode = mode
@@ -97,32 +97,77 @@ class Model:
         F.check(F.lib().ffmi_model_set_logprobs(self.handle, int(bool(enable))), "set_logprobs")
 
     def load_lora(self, A, B=None, alpha: Optional[float] = None, rank: Optional[int] = None) -> int:
-        """Load a LoRA adapter of every layer's down_proj and return its id
-        (ffmi_model_lora_load; at most F.LORA_MAX_ADAPTERS at a time, rank <=
-        F.LORA_MAX_RANK).  Either arrays, load_lora(A, B, alpha) with A
-        [num_layers][rank][intermediate] and B [num_layers][hidden][rank] as
-        HF PEFT stores lora_A.weight / lora_B.weight (cast to fp16), or a
-        folder in the reference's per-tensor format, load_lora(folder) --
-        rank and alpha then come from the folder's adapter_config.json, which
-        checkpoint.convert_peft_adapter writes, unless given.  A request names
-        the id at registration (register_new_request(..., lora_id=id))."""
+        """Load a LoRA adapter and return its id (at most F.LORA_MAX_ADAPTERS
+        at a time, rank <= F.LORA_MAX_RANK).  One of
+          load_lora(A, B, alpha): down_proj alone, A [num_layers][rank]
+            [intermediate] and B [num_layers][hidden][rank] as HF PEFT stores
+            lora_A.weight / lora_B.weight (cast to fp16; ffmi_model_lora_load);
+          load_lora({"q_proj": (A, B), "v_proj": (A, B), ...}, alpha): any of
+            q_proj, k_proj, v_proj, o_proj, down_proj, each A [num_layers]
+            [rank][in] and B [num_layers][out][rank] in the HF shapes (k / v:
+            out = num_kv_heads * head_dim), one rank for all
+            (ffmi_model_lora_load_modules); gate_proj / up_proj: FFMIError;
+          in both array forms alpha defaults to the rank (scaling 1);
+          load_lora(folder): the reference's per-tensor format, as
+            checkpoint.convert_peft_adapter writes it -- target_modules, rank
+            and alpha come from the folder's adapter_config.json, rank and
+            alpha unless given (ffmi_model_lora_load_folder_ex).
+        A request names the id at registration
+        (register_new_request(..., lora_id=id))."""
         import numpy as np
         out = ctypes.c_int(-1)
         if isinstance(A, (str, os.PathLike)):
+            import json
             folder = os.fspath(A)
-            if rank is None or alpha is None:
-                import json
-                with open(os.path.join(folder, "adapter_config.json")) as f:
+            cfg_path = os.path.join(folder, "adapter_config.json")
+            ac = {}
+            if rank is None or alpha is None or os.path.exists(cfg_path):
+                with open(cfg_path) as f:
                     ac = json.load(f)
-                rank = ac["r"] if rank is None else rank
-                alpha = ac["lora_alpha"] if alpha is None else alpha
-            F.check(F.lib().ffmi_model_lora_load_folder(self.handle, folder.encode(), int(rank),
-                                                        float(alpha), ctypes.byref(out)),
+            rank = ac["r"] if rank is None else rank
+            alpha = ac["lora_alpha"] if alpha is None else alpha
+            if ac.get("rank_pattern") or ac.get("alpha_pattern"):
+                raise ValueError("load_lora: rank_pattern / alpha_pattern adapters are not served")
+            targets = ac.get("target_modules") or ["down_proj"]
+            targets = [targets] if isinstance(targets, str) else targets
+            mask = 0
+            for t in targets:
+                if t.split(".")[-1] not in F.LORA_MODULES:
+                    raise ValueError(f"load_lora: unknown target module {t!r}")
+                mask |= 1 << F.LORA_MODULES[t.split(".")[-1]]  # (gate / up: the library refuses)
+            F.check(F.lib().ffmi_model_lora_load_folder_ex(self.handle, folder.encode(), int(rank),
+                                                           float(alpha), mask, ctypes.byref(out)),
                     "load_lora")
+            return out.value
+        c = self.config
+        if isinstance(A, dict):
+            if B is not None and alpha is not None:
+                raise ValueError("load_lora: a dict of modules takes alpha alone, load_lora(modules, alpha)")
+            if B is not None:  # load_lora(modules, alpha)
+                alpha, B = B, None
+            mods, keep, r = (F.LoraModule * max(1, len(A)))(), [], None
+            head_dim = c["hidden"] // c["num_heads"]
+            kv = c.get("num_kv_heads", c["num_heads"]) * head_dim
+            dims = {"q_proj": (c["hidden"], c["hidden"]), "k_proj": (c["hidden"], kv),
+                    "v_proj": (c["hidden"], kv), "o_proj": (c["hidden"], c["hidden"]),
+                    "down_proj": (c["intermediate"], c["hidden"])}
+            for i, (name, (a, b)) in enumerate(A.items()):
+                if name not in F.LORA_MODULES:
+                    raise ValueError(f"load_lora: unknown module {name!r}")
+                a = np.ascontiguousarray(np.asarray(a, dtype=np.float16))
+                b = np.ascontiguousarray(np.asarray(b, dtype=np.float16))
+                r = a.shape[1] if r is None and a.ndim == 3 else r
+                if name in dims and (a.shape != (c["num_layers"], r, dims[name][0]) or
+                                     b.shape != (c["num_layers"], dims[name][1], r)):
+                    raise ValueError(f"load_lora: {name} A {a.shape} / B {b.shape} do not fit the model")
+                keep += [a, b]
+                mods[i] = F.LoraModule(F.LORA_MODULES[name], a.ctypes.data, b.ctypes.data)
+            F.check(F.lib().ffmi_model_lora_load_modules(self.handle, int(r or 0),
+                                                         float((r or 0) if alpha is None else alpha),
+                                                         len(A), mods, ctypes.byref(out)), "load_lora")
             return out.value
         A = np.ascontiguousarray(np.asarray(A, dtype=np.float16))
         B = np.ascontiguousarray(np.asarray(B, dtype=np.float16))
-        c = self.config
         r = A.shape[1] if A.ndim == 3 else -1
         if A.shape != (c["num_layers"], r, c["intermediate"]) or \
                 B.shape != (c["num_layers"], c["hidden"], r):

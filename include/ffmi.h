@@ -532,16 +532,37 @@ ffmi_status ffmi_model_create(const ffmi_llama_config *cfg, const ffmi_model_opt
 #define FFMI_MODEL_NATIVE_GQA 1u
 ffmi_status ffmi_model_create_ex(const ffmi_llama_config *cfg, const ffmi_model_opts *o,
                                  unsigned flags, ffmi_model **out);
-/*   FFMI_MODEL_LORA: the model serves LoRA adapters on down_proj (the
- *   reference's LoraLinear on the MLP's down projection, lora_linear.cc),
- *   one adapter per request at most, requests of different adapters and of
- *   none in one batch.  fp16 INC and TREE models at tp_size 1 only: BEAM
- *   (SSMs run without adapters), full_precision and tp_size > 1 return
- *   FFMI_ERR_UNSUPPORTED ("lora" in ffmi_last_error).  In a step where some
- *   row has an adapter, down_proj runs outside the fused residual norms, its
- *   split-K sums are rounded to fp16 [T][H] and ffmi_lora_apply follows on
- *   that (FFMI_DBG_DOWN then holds the adapted output); a step without
- *   adapters is the step of a model without the flag, launch for launch. */
+/*   FFMI_MODEL_LORA: the model serves LoRA adapters on the attention
+ *   projections q_proj, k_proj, v_proj, o_proj and on down_proj (the
+ *   reference's LoraLinear, lora_linear.cc; gate_proj / up_proj are not
+ *   served), one adapter per request at most, requests of different adapters
+ *   and of none in one batch.  fp16 INC and TREE models at tp_size 1 only:
+ *   BEAM (SSMs run without adapters), full_precision and tp_size > 1 return
+ *   FFMI_ERR_UNSUPPORTED ("lora" in ffmi_last_error).  A step's module mask is
+ *   the union of the modules of the adapters its rows name; a row without an
+ *   adapter keeps the bits it has in a step without adapters.  The route of
+ *   each module in the mask:
+ *     q / k / v: the attention norm runs as a launch, the qkv GEMM rounds its
+ *       split-K sums to fp16 [T][Nqkv] and ffmi_lora_apply_qkv follows on
+ *       that row, ahead of RoPE and the KV store (FFMI_DBG_QKV then holds the
+ *       adapted row);
+ *     o: where the o projection is folded into the attention it stays there
+ *       (its per-head slabs are then summed in head order and rounded once,
+ *       the value the residual norm computes from them); otherwise the o GEMM
+ *       runs outside the fused residual norms, its split-K sums rounded to
+ *       fp16 [T][H].  ffmi_lora_apply follows on that with x the attention
+ *       output, then the residual norm as a launch (FFMI_DBG_O_PROJ: adapted);
+ *     down: down_proj runs outside the fused residual norms, its split-K sums
+ *       are rounded to fp16 [T][H] and ffmi_lora_apply follows on that
+ *       (FFMI_DBG_DOWN then holds the adapted output).
+ *   A step with an empty mask is the step of a model without the flag, launch
+ *   for launch, with one exception: the fused residual norms are not
+ *   bit-identical to the norm launches, so on a model that uses them (hidden
+ *   >= 2048 by default, FFMI_FUSE_NORM) the route is decided at load time --
+ *   while an adapter with an attention module (q, k, v, o) is resident, every
+ *   step takes the routes above of all of that adapter's modules, whatever
+ *   its rows name.  (A down-only adapter keeps its per-step route: a step
+ *   that names none is the fused step.) */
 /*   (bit value 4: 2 stays an unknown flag, FFMI_ERR_INVALID, as it was before
  *   the adapters came and as callers written against that may rely on) */
 #define FFMI_MODEL_LORA 4u
@@ -552,14 +573,32 @@ ffmi_status ffmi_model_create_ex(const ffmi_llama_config *cfg, const ffmi_model_
  *   HF PEFT stores lora_A.weight / lora_B.weight of every layer's down_proj;
  *   scaling = fp16(alpha / rank).  1 <= rank <= FFMI_LORA_MAX_RANK (stored
  *   zero-padded); a larger rank: FFMI_ERR_UNSUPPORTED ("lora").  No free id:
- *   FFMI_ERR_OOM.  Device storage is allocated here, never in a step.
+ *   FFMI_ERR_OOM.  Device storage is allocated here, never in a step.  The
+ *   one-module (down) case of load_modules.
+ *   load_modules: n modules of one adapter, each once, one rank and one alpha
+ *   for all (PEFT's rank_pattern is not served).  A [L][rank][in] and B
+ *   [L][out][rank] fp16 host arrays in the HF shapes: q (in H, out H), k and v
+ *   (H, num_kv_heads * head_dim), o (H, H), down (F, H).  Under the default
+ *   replicated load of a GQA checkpoint the rows of a k / v B are replicated
+ *   to the query heads as the loader replicates the k / v weights (query head
+ *   h uses K/V head h / G); under FFMI_MODEL_NATIVE_GQA they are taken as
+ *   stored.  n == 0, a module twice or an unknown module id: FFMI_ERR_INVALID;
+ *   FFMI_LORA_GATE / FFMI_LORA_UP: FFMI_ERR_UNSUPPORTED (their GEMM's SiLU-mul
+ *   epilogue never leaves the pre-activation values in memory); "lora" in
+ *   ffmi_last_error in both cases.
  *   load_folder: the reference's per-tensor files
  *   layers.{i}.mlp.down_proj.lora_A.weight / .lora_B.weight in `folder`
  *   (peft_weight_allocator.cc:171-240), fp16 or fp32 by file size.  A file of
  *   another target module in the folder (q_proj, up_proj, ...):
- *   FFMI_ERR_UNSUPPORTED ("lora").
+ *   FFMI_ERR_UNSUPPORTED ("lora").  The modules == FFMI_LORA_DOWN_BIT case of
+ *   load_folder_ex.
+ *   load_folder_ex: layers.{i}.self_attn.{q,k,v,o}_proj.lora_{A,B}.weight and
+ *   layers.{i}.mlp.down_proj.lora_{A,B}.weight of the modules in the mask
+ *   `modules` (FFMI_LORA_*_BIT).  FFMI_ERR_UNSUPPORTED ("lora"): a .lora_ file
+ *   of a module outside the mask or of gate_proj / up_proj in the folder, a
+ *   file of a module in the mask missing or of the wrong size.
  *   unload: FFMI_ERR_INVALID while a registered, unfinished request names the
- *   adapter, or for an id this model did not load. */
+ *   adapter, or for an id this model did not load; frees every module. */
 #define FFMI_LORA_MAX_ADAPTERS 8
 #define FFMI_LORA_MAX_RANK 64
 ffmi_status ffmi_model_lora_load(ffmi_model *m, int rank, float alpha, const void *A,
@@ -567,6 +606,27 @@ ffmi_status ffmi_model_lora_load(ffmi_model *m, int rank, float alpha, const voi
 ffmi_status ffmi_model_lora_load_folder(ffmi_model *m, const char *folder, int rank, float alpha,
                                         int *id_out);
 ffmi_status ffmi_model_lora_unload(ffmi_model *m, int id);
+/* module ids of an adapter and their bit masks (1u << id) */
+#define FFMI_LORA_Q 0
+#define FFMI_LORA_K 1
+#define FFMI_LORA_V 2
+#define FFMI_LORA_O 3
+#define FFMI_LORA_DOWN 4
+#define FFMI_LORA_GATE 5 /* refused */
+#define FFMI_LORA_UP 6   /* refused */
+#define FFMI_LORA_Q_BIT (1u << FFMI_LORA_Q)
+#define FFMI_LORA_K_BIT (1u << FFMI_LORA_K)
+#define FFMI_LORA_V_BIT (1u << FFMI_LORA_V)
+#define FFMI_LORA_O_BIT (1u << FFMI_LORA_O)
+#define FFMI_LORA_DOWN_BIT (1u << FFMI_LORA_DOWN)
+typedef struct {
+  int module; /* FFMI_LORA_Q .. FFMI_LORA_DOWN */
+  const void *A, *B;
+} ffmi_lora_module;
+ffmi_status ffmi_model_lora_load_modules(ffmi_model *m, int rank, float alpha, int n,
+                                         const ffmi_lora_module *mods, int *id_out);
+ffmi_status ffmi_model_lora_load_folder_ex(ffmi_model *m, const char *folder, int rank,
+                                           float alpha, unsigned modules, int *id_out);
 /* The LoRA update of a [T][H] fp16 projection output, in place:
  *   h[t][j]  = fp16(sum_k x[t][k] A[j][k])            (fp32 accumulation)
  *   y[t][n]  = fp16(float(y[t][n]) + scale * sum_j h[t][j] B[n][j])
@@ -592,6 +652,26 @@ size_t ffmi_lora_workspace_bytes(int T, int F);
 ffmi_status ffmi_lora_apply(const void *x, int T, int F, int H, const int32_t *slots,
                             const ffmi_lora_entry *table, void *y, int x_packed, void *ws,
                             size_t ws_bytes, void *h_out, ffmi_stream stream);
+/* The same update of the fused qkv row y [T][ldy] = [Q | K | V], the segments
+ * seg_width[0..2] columns wide, from one x [T][in_dim] (the attention norm's
+ * output), in two launches for the three modules.  table[s]: the
+ * FFMI_LORA_MAX_ADAPTERS device-resident entries of segment s (A packed from
+ * [64][in_dim], B [seg_width[s]][64]); an entry with NULL A or B: the adapter
+ * has no such module, and the row's columns of that segment are not written.
+ * A row's bits depend on the row, its adapter and the module's dimensions
+ * only: not on T, the rows around it or which other segments are present, and
+ * they are those of ffmi_lora_apply(x, T, in_dim, seg_width[s]) on the
+ * segment alone.  Columns [sum of the widths, ldy) are not touched.
+ *   ws: ffmi_lora_qkv_workspace_bytes(T, in_dim) = 3 * ceil(in_dim / 256) * T
+ *   * 64 floats.  h_out: NULL, or [3][T][64] fp16, written where the row's
+ *   adapter has the segment's module.
+ * FFMI_ERR_INVALID: in_dim % 32, a width that is not a positive multiple of 8,
+ * ldy below the sum of the widths, a missing or short workspace. */
+size_t ffmi_lora_qkv_workspace_bytes(int T, int in_dim);
+ffmi_status ffmi_lora_apply_qkv(const void *x, int T, int in_dim, const int *seg_width,
+                                const int32_t *slots, const ffmi_lora_entry *const *table,
+                                void *y, int ldy, int x_packed, void *ws, size_t ws_bytes,
+                                void *h_out, ffmi_stream stream);
 /* bytes of the K plus V caches of all layers (this rank's; fp16 models) */
 size_t ffmi_model_kv_cache_bytes(ffmi_model *m);
 void ffmi_model_destroy(ffmi_model *m);
@@ -944,7 +1024,9 @@ const char *ffmi_last_error(void);
  * and per-token log-probabilities: ffmi_token_logprobs(_workspace_bytes),
  * ffmi_model_set_logprobs, ffmi_rm_get_logprobs; and LoRA adapters on
  * down_proj: FFMI_MODEL_LORA, ffmi_model_lora_load(_folder) / _unload,
- * ffmi_lora_apply(_workspace_bytes), ffmi_rm_register_request_ex */
+ * ffmi_lora_apply(_workspace_bytes), ffmi_rm_register_request_ex; and on the
+ * attention projections: ffmi_model_lora_load_modules, _load_folder_ex,
+ * ffmi_lora_apply_qkv, ffmi_lora_qkv_workspace_bytes */
 const char *ffmi_version(void);
 
 #ifdef __cplusplus
