@@ -55,7 +55,9 @@ extern "C" const char *ffmi_status_str(ffmi_status s) {
 // ffmi_attn_create_gqa, ffmi_attn_cache_bytes, ffmi_attn_set_gqa_route,
 // ffmi_model_create_ex (FFMI_MODEL_NATIVE_GQA), ffmi_model_kv_cache_bytes;
 // then per-token log-probabilities, by addition only: ffmi_token_logprobs,
-// ffmi_token_logprobs_workspace_bytes, ffmi_model_set_logprobs, ffmi_rm_get_logprobs
+// ffmi_token_logprobs_workspace_bytes, ffmi_model_set_logprobs, ffmi_rm_get_logprobs;
+// then the 8-bit KV cache, by addition only: ffmi_attn_create_ex (FFMI_ATTN_KV_FP8),
+// FFMI_MODEL_KV_FP8, ffmi_model_set_kv_scales
 extern "C" const char *ffmi_version(void) { return "ffmi 0.4 (gfx950)"; }
 
 // ---------------------------------------------------------------------------
@@ -260,6 +262,9 @@ struct ffmi_attn {
   // (== cfg.num_heads: MHA, every launch as before), and the route hook
   int kv_heads = 0;
   int gqa_route = 0;  // 0 auto, 1 kv-indexed, 2 group-shared where eligible
+  // FFMI_ATTN_KV_FP8 (ffmi_attn_create_ex): kc / vc are the byte caches
+  bool kv_fp8 = false;
+  float k_scale = 1.f, v_scale = 1.f;
 };
 static_assert(offsetof(ffmi_attn, cfg) == 0, "ffmi_attn starts with its cfg (test_partials_cpu.py)");
 
@@ -305,7 +310,8 @@ static void rope_table(std::vector<float> &tab, int max_pos, int d, const ffmi_a
     }
 }
 
-static ffmi_status attn_create(const ffmi_attn_cfg *cfg, int kv_heads, ffmi_attn **out) {
+static ffmi_status attn_create(const ffmi_attn_cfg *cfg, int kv_heads, ffmi_attn **out,
+                               bool kv_fp8 = false, float k_scale = 1.f, float v_scale = 1.f) {
   FFMI_CHECK(cfg && out, FFMI_ERR_INVALID);
   // head sizes of the reference's kernels: 32 / 64 / 128 for incremental
   // decoding (inc_multihead_self_attention.cu:911-926), 64 / 128 for tree
@@ -322,6 +328,7 @@ static ffmi_status attn_create(const ffmi_attn_cfg *cfg, int kv_heads, ffmi_attn
   ffmi_attn *h = new ffmi_attn();
   h->cfg = *cfg;
   h->kv_heads = kv_heads;
+  h->kv_fp8 = kv_fp8, h->k_scale = k_scale, h->v_scale = v_scale;
   h->slots = (cfg->max_seq_len + cfg->max_tree_tokens + 31) & ~31;
   const size_t Hl = (size_t)cfg->num_heads * cfg->head_dim;
   const size_t Hkv = (size_t)kv_heads * cfg->head_dim;  // (== Hl for MHA)
@@ -336,8 +343,11 @@ static ffmi_status attn_create(const ffmi_attn_cfg *cfg, int kv_heads, ffmi_attn
     return FFMI_ERR_UNSUPPORTED;
   }
   const size_t es = f32 ? 4 : 2, stage_halves = f32 ? 1 : 2;
-  bool ok = hipMalloc((void **)&h->kc, kv * es) == hipSuccess &&
-            hipMalloc((void **)&h->vc, kv * es) == hipSuccess &&
+  // (an 8-bit cache: one byte per element, the zero byte is e4m3's 0.0; q and
+  // the staging rows stay fp16)
+  const size_t ces = kv_fp8 ? 1 : es;
+  bool ok = hipMalloc((void **)&h->kc, kv * ces) == hipSuccess &&
+            hipMalloc((void **)&h->vc, kv * ces) == hipSuccess &&
             hipMalloc((void **)&h->qbuf, (size_t)cfg->max_tokens * Hl * es) == hipSuccess;
   if (ok && cfg->mode == FFMI_ATTN_TREE)
     ok = hipMalloc((void **)&h->stage, (size_t)cfg->max_tokens * 2 * Hkv * es * stage_halves) ==
@@ -354,8 +364,8 @@ static ffmi_status attn_create(const ffmi_attn_cfg *cfg, int kv_heads, ffmi_attn
   // an exactly-zero weight, so a slot there must hold finite values (its
   // request has written it; slots at and past kv_len, where a recycled request
   // slot keeps its last occupant's rows, enter no product: attention.hip)
-  FFMI_HIP(hipMemset(h->kc, 0, kv * es));
-  FFMI_HIP(hipMemset(h->vc, 0, kv * es));
+  FFMI_HIP(hipMemset(h->kc, 0, kv * ces));
+  FFMI_HIP(hipMemset(h->vc, 0, kv * ces));
   if (h->stage)
     FFMI_HIP(hipMemset(h->stage, 0, (size_t)cfg->max_tokens * 2 * Hkv * es * stage_halves));
   FFMI_HIP(hipMemcpy(h->rope, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
@@ -388,10 +398,45 @@ extern "C" ffmi_status ffmi_attn_create_gqa(const ffmi_attn_cfg *cfg, int num_kv
   return attn_create(cfg, num_kv_heads, out);
 }
 
+// An 8-bit (e4m3) KV cache behind the same entry points (include/ffmi.h).
+// The refusals precede every HIP call.
+static bool kv_scale_ok(float s) { return s > 0.f && std::isfinite(s); }
+
+extern "C" ffmi_status ffmi_attn_create_ex(const ffmi_attn_cfg *cfg, int num_kv_heads,
+                                           unsigned flags, float k_scale, float v_scale,
+                                           ffmi_attn **out) {
+  if (!flags) return ffmi_attn_create_gqa(cfg, num_kv_heads, out);
+  FFMI_CHECK(cfg && out, FFMI_ERR_INVALID);
+  const char *why = nullptr;
+  ffmi_status st = FFMI_ERR_INVALID;
+  if (flags & ~FFMI_ATTN_KV_FP8) why = "kv_fp8: unknown ffmi_attn_create_ex flag";
+  else if (!kv_scale_ok(k_scale) || !kv_scale_ok(v_scale))
+    why = "kv_fp8: k_scale and v_scale must be finite and > 0";
+  else if (cfg->full_precision)
+    why = "kv_fp8: fp16 handles only (full_precision)", st = FFMI_ERR_UNSUPPORTED;
+  else if (cfg->head_dim != 64 && cfg->head_dim != 128)
+    why = "kv_fp8: head_dim 64 or 128", st = FFMI_ERR_UNSUPPORTED;
+  if (why) {
+    ffmi_set_last_error(why, __FILE__, __LINE__);
+    return st;
+  }
+  if (num_kv_heads <= 0) num_kv_heads = cfg->num_heads;
+  FFMI_CHECK(cfg->num_heads > 0 && cfg->num_heads % num_kv_heads == 0, FFMI_ERR_INVALID);
+  return attn_create(cfg, num_kv_heads, out, true, k_scale, v_scale);
+}
+
+namespace ffmi {
+ffmi_status attn_set_kv_scales(ffmi_attn *h, float k_scale, float v_scale) {
+  FFMI_CHECK(h && h->kv_fp8 && kv_scale_ok(k_scale) && kv_scale_ok(v_scale), FFMI_ERR_INVALID);
+  h->k_scale = k_scale, h->v_scale = v_scale;
+  return FFMI_OK;
+}
+}  // namespace ffmi
+
 extern "C" size_t ffmi_attn_cache_bytes(ffmi_attn *h) {
   if (!h) return 0;
   return (size_t)2 * h->cfg.max_requests * h->kv_heads * h->slots * h->cfg.head_dim *
-         (h->cfg.full_precision ? 4 : 2);
+         (h->kv_fp8 ? 1 : h->cfg.full_precision ? 4 : 2);
 }
 
 extern "C" ffmi_status ffmi_attn_set_gqa_route(ffmi_attn *h, int route) {
@@ -472,6 +517,26 @@ ffmi_status attn_forward(ffmi_attn *h, const ffmi_batch_dev *b, const void *qkv,
     stage_wr = h->stage + (parity ? half : 0);
     stage_rd = h->stage + (parity ? 0 : half);
     C = b->num_commits;
+  }
+  if (h->kv_fp8) {
+    // An 8-bit cache: always the KV-update launch, then the fp8-reading
+    // attention (no LDS tail, no folded o projection -- opa->done stays false
+    // and the caller runs its GEMM -- no query split, GQA kv-indexed).  The
+    // commit-then-store order as below.
+    uint8_t *k8 = reinterpret_cast<uint8_t *>(h->kc), *v8 = reinterpret_cast<uint8_t *>(h->vc);
+    if (C > 0 && b->commit_overlap) {
+      FFMI_HIP(ffmi::launch_commit_fp8(b->dev, C, stage_rd, k8, v8, kvh, d, h->slots, h->k_scale,
+                                       h->v_scale, s));
+      C = 0;
+    }
+    FFMI_HIP(ffmi::launch_kv_update_fp8(b->dev, b->num_tokens, b->num_work, C,
+                                        (const uint16_t *)qkv, qkvp, h->qbuf, k8, v8, stage_wr,
+                                        stage_rd, h->rope, heads, d, h->slots, h->slots, kvh,
+                                        h->k_scale, h->v_scale, s));
+    FFMI_HIP(ffmi::launch_attention_fp8(b->dev, b->num_work, b->max_q, h->qbuf, k8, v8,
+                                        (uint16_t *)out, heads, d, h->slots, h->cfg.qk_scale,
+                                        h->k_scale, h->v_scale, h->cfg.out_layout == 1, kvh, s));
+    return FFMI_OK;
   }
   // One work item per request (decode, SSM beam steps, tree verify): commits
   // + KV update + attention in one launch.  Otherwise (prefill blocks) the

@@ -324,6 +324,23 @@ hipError_t launch_attention(const char *blob, int W, int max_q, uint16_t *qbuf, 
                             const OprojArgs *opa = nullptr, int kv_heads = 0,
                             bool gqa_shared = false);  // (a GQA handle: its K/V heads, its form)
 
+// An FFMI_ATTN_KV_FP8 handle's three launches: byte caches K8[req][kv head][slot][d]
+// and V8T[req][kv head][d][slot] of e4m3(x / scale); q, the staging rows and the
+// output stay fp16.  Always the two-launch route (kv_heads: 0 / heads for MHA;
+// a GQA handle takes fp16 qkv rows and the kv-indexed form); d 64 / 128.
+hipError_t launch_commit_fp8(const char *blob, int C, const uint16_t *stage, uint8_t *kc,
+                             uint8_t *vc, int kv_heads, int d, int slots, float k_scale,
+                             float v_scale, hipStream_t s);
+hipError_t launch_kv_update_fp8(const char *blob, int T, int W, int C, const uint16_t *qkv,
+                                Partials qkvp, uint16_t *qbuf, uint8_t *kc, uint8_t *vc,
+                                uint16_t *stage_wr, const uint16_t *stage_rd, const float *rope,
+                                int heads, int d, int slots, int max_rope_pos, int kv_heads,
+                                float k_scale, float v_scale, hipStream_t s);
+hipError_t launch_attention_fp8(const char *blob, int W, int max_q, const uint16_t *qbuf,
+                                const uint8_t *kc, const uint8_t *vc, uint16_t *out, int heads,
+                                int d, int slots, float scale, float k_scale, float v_scale,
+                                bool out_packed, int kv_heads, hipStream_t s);
+
 uint64_t weight_key(const char *name, uint64_t seed);
 
 }  // namespace ffmi
@@ -392,4 +409,6 @@ ffmi_status comm_status(ffmi_comm *c);
 ffmi_status attn_forward(ffmi_attn *h, const ffmi_batch_dev *b, const void *qkv, Partials qkvp,
                          void *out, ffmi_stream stream, int parity = -1,
                          OprojArgs *opa = nullptr);
+// the static scales of an FFMI_ATTN_KV_FP8 handle whose caches hold nothing yet
+ffmi_status attn_set_kv_scales(ffmi_attn *h, float k_scale, float v_scale);
 }  // namespace ffmi

@@ -41,12 +41,9 @@
 
 #include <algorithm>
 
-#include "../ffmi_internal.h"
+#include "attention_util.h"
 
 namespace ffmi {
-
-__device__ __forceinline__ float h2f(uint16_t v) { return __half2float(__ushort_as_half(v)); }
-__device__ __forceinline__ uint16_t f2h(float v) { return __half_as_ushort(__float2half_rn(v)); }
 
 // commit_tokens_kernel (tree_inc...cu:335-396): accepted tokens of the
 // previous verify batch move from the staging rows to their depth slot.
@@ -112,8 +109,12 @@ __device__ __forceinline__ void st_h4(uint16_t *p, uint16_t a, uint16_t b, uint1
 // a staging row holds 2 kvh D values.  GS (the group-shared form): the NQ
 // units' rows are tile rows r = q * gq + m -- token q of the item, query head
 // hk * gq + m -- and only a token's m == 0 row stores its K/V.
-template <int D, int NQ, int NT, int PSRC = -1, bool GS = false, class AfterLoads,
-          class BeforeStores>
+// F8 (an FFMI_ATTN_KV_FP8 handle; never with a tail): kc is the byte cache
+// K8[req][kv head][slot][D]; a unit's rotated K goes out as 4 + 4 packed e4m3
+// bytes of k / k8s, and its V as e4m3 bytes of v / v8s into the sV tile (one
+// per element, for kv_store_vt8).  q and the staging rows stay fp16.
+template <int D, int NQ, int NT, int PSRC = -1, bool GS = false, bool F8 = false,
+          class AfterLoads, class BeforeStores>
 __device__ __forceinline__ void kv_update_item(
     const BatchView &bv, const WorkDev *__restrict__ wdp, int h, int heads, int hk, int kvh,
     int gq, int slots, int T,
@@ -122,7 +123,7 @@ __device__ __forceinline__ void kv_update_item(
     uint16_t *__restrict__ kc, uint16_t *__restrict__ stage_wr, uint16_t (*sV)[NQ + 1],
     int *sSlot, uint16_t (*sQ)[D + 8], uint16_t (*sKt)[D + 8],
     uint16_t (*sVt)[kTailSlots + 8], int tail0, AfterLoads &&after_loads,
-    BeforeStores &&before_stores) {
+    BeforeStores &&before_stores, float k8s = 1.f, float v8s = 1.f) {
   constexpr int HD = D / 2, G = HD / 4, UNITS = NQ * G, U = (UNITS + NT - 1) / NT;
   const int Hl = heads * D, Hkv = kvh * D, RW = Hl + 2 * Hkv;
   const ffmi_attn_work w = wdp->w;
@@ -252,13 +253,28 @@ __device__ __forceinline__ void kv_update_item(
     st_h4(qo + HD, qhi[0], qhi[1], qhi[2], qhi[3]);
     if (GS && tl[u] % gq != 0) continue;  // the token's K/V: its first row only
     const bool store = tslot[u] >= 0 && tslot[u] < slots;
-    if (store) {
+    if (F8) {
+      if (store) {
+        uint8_t *kr = reinterpret_cast<uint8_t *>(kc) +
+                      (((size_t)treq[u] * kvh + hk) * slots + tslot[u]) * D + i0[u];
+        *reinterpret_cast<uint32_t *>(kr) = kv8_quant_h4(klo[0], klo[1], klo[2], klo[3], k8s);
+        *reinterpret_cast<uint32_t *>(kr + HD) = kv8_quant_h4(khi[0], khi[1], khi[2], khi[3], k8s);
+      }
+      const uint32_t a = kv8_quant_h4(vlo[0], vlo[1], vlo[2], vlo[3], v8s);
+      const uint32_t b = kv8_quant_h4(vhi[0], vhi[1], vhi[2], vhi[3], v8s);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        sV[i0[u] + j][tq[u]] = (a >> (8 * j)) & 0xffu;
+        sV[i0[u] + HD + j][tq[u]] = (b >> (8 * j)) & 0xffu;
+      }
+    } else if (store) {
       uint16_t *kr = kc + (((size_t)treq[u] * kvh + hk) * slots + tslot[u]) * D + i0[u];
       st_h4(kr, klo[0], klo[1], klo[2], klo[3]);
       st_h4(kr + HD, khi[0], khi[1], khi[2], khi[3]);
     }
     if (i0[u] == 0) sSlot[tq[u]] = store ? tslot[u] : -1;
-    if (sKt) {  // (host-checked: every stored slot lies in the tail)
+    // (F8 has no tail form: the block is compiled out, whatever sKt is)
+    if (!F8 && sKt) {  // (host-checked: every stored slot lies in the tail)
       if (store) {
         const int ts = tslot[u] - tail0;
         st_h4(&sKt[ts][i0[u]], klo[0], klo[1], klo[2], klo[3]);
@@ -269,7 +285,7 @@ __device__ __forceinline__ void kv_update_item(
           sVt[i0[u] + HD + j][ts] = vhi[j];
         }
       }
-    } else {
+    } else if (!F8) {
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         sV[i0[u] + j][tq[u]] = vlo[j];
@@ -347,6 +363,148 @@ __global__ __launch_bounds__(FFMI_ATTN_QTILE * D / 8) void kv_update_kernel(
   kv_store_vt<D, NQ>(w, hk, kvh, slots, vc, sV, sSlot);
 }
 
+// ---- an FFMI_ATTN_KV_FP8 handle's KV update and commits (byte caches
+// K8[req][kv head][slot][d] and V8T[req][kv head][d][slot]; attention_util.h)
+
+// V8T rows from the tile's bytes.  A thread takes four tokens of a d-row,
+// grouped so that an item stored to consecutive slots gives 4-byte-aligned
+// groups: one dword store where the four go to consecutive slots, byte stores
+// otherwise (a decode step's single token, an item's ragged ends).
+template <int D, int NQ>
+__device__ __forceinline__ void kv_store_vt8(const ffmi_attn_work &w, int h, int heads, int slots,
+                                             uint8_t *__restrict__ vc,
+                                             const uint16_t (*sV)[NQ + 1], const int *sSlot) {
+  uint8_t *vt = vc + ((size_t)w.req * heads + h) * D * slots;
+  const int off = sSlot[0] >= 0 ? sSlot[0] & 3 : 0;
+  constexpr int NG = NQ / 4 + 1;
+  for (int e = threadIdx.x; e < D * NG; e += blockDim.x) {
+    const int dd = e / NG, t0 = (e % NG) * 4 - off;
+    int sl[4];
+    uint32_t pk = 0;
+    bool run = true;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int tt = t0 + j;
+      const bool valid = tt >= 0 && tt < w.q_count;
+      const int tc = min(max(tt, 0), NQ - 1);  // (no LDS read out of the tile)
+      sl[j] = valid ? sSlot[tc] : -1;
+      pk |= valid ? (uint32_t)sV[dd][tc] << (8 * j) : 0u;
+      run = run && sl[j] >= 0 && sl[j] == sl[0] + j;
+    }
+    uint8_t *row = vt + (size_t)dd * slots;
+    if (run && (sl[0] & 3) == 0) {
+      *reinterpret_cast<uint32_t *>(row + sl[0]) = pk;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (sl[j] >= 0) row[sl[j]] = (uint8_t)(pk >> (8 * j));
+    }
+  }
+}
+
+// one commit for one K/V head: the quantiser over the fp16 staging row, so the
+// depth slot gets exactly the bytes the verify step stored in the tree slot.
+// Thread i < D / 4 takes d = 4 i .. 4 i + 3: a dword of the K row, four V8T bytes.
+template <int D>
+__device__ __forceinline__ void commit_item8(const ffmi_commit_info &cm,
+                                             const uint16_t *__restrict__ stage, uint8_t *kc,
+                                             uint8_t *vc, int kvh, int hk, int slots, float k8s,
+                                             float v8s, int i) {
+  if (cm.depth < 0 || cm.depth >= slots || i >= D / 4) return;
+  const int Hkv = kvh * D;
+  const uint16_t *st = stage + (size_t)cm.src_token * 2 * Hkv + hk * D + 4 * i;
+  const uint2 kb = *reinterpret_cast<const uint2 *>(st);
+  const uint2 vb = *reinterpret_cast<const uint2 *>(st + Hkv);
+  *reinterpret_cast<uint32_t *>(kc + (((size_t)cm.req * kvh + hk) * slots + cm.depth) * D + 4 * i) =
+      kv8_quant_h4(kb.x & 0xffff, kb.x >> 16, kb.y & 0xffff, kb.y >> 16, k8s);
+  const uint32_t v4 = kv8_quant_h4(vb.x & 0xffff, vb.x >> 16, vb.y & 0xffff, vb.y >> 16, v8s);
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    vc[(((size_t)cm.req * kvh + hk) * D + 4 * i + j) * slots + cm.depth] = (uint8_t)(v4 >> (8 * j));
+}
+
+template <int D>
+__global__ FFMI_NO_PK_F32 void commit_fp8_kernel(const char *__restrict__ blob, int C,
+                                  const uint16_t *__restrict__ stage, uint8_t *__restrict__ kc,
+                                  uint8_t *__restrict__ vc, int kvh, int slots, float k8s,
+                                  float v8s) {
+  const int ci = blockIdx.x / kvh, hk = blockIdx.x % kvh;
+  if (ci >= C) return;
+  commit_item8<D>(batch_view(blob).commits[ci], stage, kc, vc, kvh, hk, slots, k8s, v8s,
+                  threadIdx.x);
+}
+
+// kv_update_kernel with the quantising stores; grid, item and commit blocks
+// as there (GQ: the members of a group store the same bytes to the same
+// addresses)
+template <int D, bool GQ>
+__global__ __launch_bounds__(FFMI_ATTN_QTILE * D / 8) FFMI_NO_PK_F32 void kv_update_fp8_kernel(
+    const char *__restrict__ blob, int T, int W, int C, const uint16_t *__restrict__ qkv,
+    const float *__restrict__ part, int pS, int pNP, uint16_t *__restrict__ qbuf,
+    uint8_t *__restrict__ kc, uint8_t *__restrict__ vc, uint16_t *__restrict__ stage_wr,
+    const uint16_t *__restrict__ stage_rd, const float *__restrict__ rope, int heads, int slots,
+    int max_rope_pos, int kvh_, float k8s, float v8s) {
+  constexpr int NQ = FFMI_ATTN_QTILE;
+  constexpr int NT = NQ * D / 8;
+  __shared__ uint16_t sV[D][NQ + 1];
+  __shared__ int sSlot[NQ];
+  const BatchView bv = batch_view(blob);
+  const int item = blockIdx.x / heads, h = blockIdx.x % heads;
+  const int kvh = GQ ? kvh_ : heads, gq = GQ ? heads / kvh_ : 1, hk = GQ ? h / gq : h;
+  if (item >= W) {
+    if (item - W < C)
+      commit_item8<D>(bv.commits[item - W], stage_rd, kc, vc, kvh, hk, slots, k8s, v8s,
+                      threadIdx.x);
+    return;
+  }
+  const ffmi_attn_work w = bv.work[item].w;
+  kv_update_item<D, NQ, NT, -1, false, true>(
+      bv, &bv.work[item], h, heads, hk, kvh, gq, slots, T, qkv, part, pS, pNP, rope, max_rope_pos,
+      qbuf, reinterpret_cast<uint16_t *>(kc), stage_wr, sV, sSlot, nullptr, nullptr, nullptr, 0,
+      [] {}, [] {}, k8s, v8s);
+  __syncthreads();
+  kv_store_vt8<D, NQ>(w, hk, kvh, slots, vc, sV, sSlot);
+}
+
+hipError_t launch_commit_fp8(const char *blob, int C, const uint16_t *stage, uint8_t *kc,
+                             uint8_t *vc, int kv_heads, int d, int slots, float k_scale,
+                             float v_scale, hipStream_t s) {
+  if (C <= 0) return hipSuccess;
+  if (d == 128)
+    hipLaunchKernelGGL(commit_fp8_kernel<128>, dim3(C * kv_heads), dim3(64), 0, s, blob, C, stage,
+                       kc, vc, kv_heads, slots, k_scale, v_scale);
+  else if (d == 64)
+    hipLaunchKernelGGL(commit_fp8_kernel<64>, dim3(C * kv_heads), dim3(64), 0, s, blob, C, stage,
+                       kc, vc, kv_heads, slots, k_scale, v_scale);
+  else
+    return hipErrorInvalidValue;
+  return hipGetLastError();
+}
+
+hipError_t launch_kv_update_fp8(const char *blob, int T, int W, int C, const uint16_t *qkv,
+                                Partials qkvp, uint16_t *qbuf, uint8_t *kc, uint8_t *vc,
+                                uint16_t *stage_wr, const uint16_t *stage_rd, const float *rope,
+                                int heads, int d, int slots, int max_rope_pos, int kv_heads,
+                                float k_scale, float v_scale, hipStream_t s) {
+  if (W <= 0 && C <= 0) return hipSuccess;
+  const bool gqa = kv_heads > 0 && kv_heads != heads;
+  const float *pp = qkvp.S > 0 ? qkvp.p : nullptr;
+  // (slabs on a GQA handle: the launcher's own guard only -- attn_forward, the
+  // one caller, refuses them for every GQA handle, fp8 or not, with its message)
+  if ((d != 128 && d != 64) || (gqa && (heads % kv_heads || pp))) return hipErrorInvalidValue;
+  const dim3 grid((W + C) * heads), block(FFMI_ATTN_QTILE * d / 8);
+#define FFMI_KVU8(D, GQ)                                                                        \
+  hipLaunchKernelGGL((kv_update_fp8_kernel<D, GQ>), grid, block, 0, s, blob, T, W, C, qkv, pp,  \
+                     qkvp.S, qkvp.NP, qbuf, kc, vc, stage_wr, stage_rd, rope, heads, slots,     \
+                     max_rope_pos, gqa ? kv_heads : heads, k_scale, v_scale)
+  if (d == 128 && gqa) FFMI_KVU8(128, true);
+  else if (d == 128) FFMI_KVU8(128, false);
+  else if (gqa) FFMI_KVU8(64, true);
+  else FFMI_KVU8(64, false);
+#undef FFMI_KVU8
+  return hipGetLastError();
+}
+
 hipError_t launch_kv_update(const char *blob, int T, int W, int C, const uint16_t *qkv,
                             Partials qkvp, uint16_t *qbuf, uint16_t *kc, uint16_t *vc,
                             uint16_t *stage_wr, const uint16_t *stage_rd, const float *rope,
@@ -382,14 +540,6 @@ hipError_t launch_kv_update(const char *blob, int T, int W, int C, const uint16_
   else
     return hipErrorInvalidValue;
   return hipGetLastError();
-}
-
-// visibility from registers only: prefix range + the query's 64-bit tree word
-__device__ __forceinline__ bool key_visible(int slot, int prefix_len, int tree_base,
-                                            int tree_len, uint64_t tree_vis) {
-  const unsigned j = (unsigned)(slot - tree_base);
-  const bool in_tree = j < (unsigned)tree_len && ((tree_vis >> (j & 63)) & 1ull);
-  return (slot < prefix_len) | in_tree;  // no branches: one select per key
 }
 
 // Arguments of the fused prologue (FUSED kernels only; see attention_kernel).

@@ -20,8 +20,13 @@ extern "C" ffmi_status ffmi_model_create(const ffmi_llama_config *cfg, const ffm
 extern "C" ffmi_status ffmi_model_create_ex(const ffmi_llama_config *cfg, const ffmi_model_opts *o,
                                             unsigned flags, ffmi_model **out) {
   if (!flags) return ffmi_model_create(cfg, o, out);
-  FFMI_CHECK(cfg && o && out && (flags & ~(FFMI_MODEL_NATIVE_GQA | FFMI_MODEL_LORA)) == 0,
+  FFMI_CHECK(cfg && o && out &&
+                 (flags & ~(FFMI_MODEL_NATIVE_GQA | FFMI_MODEL_LORA | FFMI_MODEL_KV_FP8)) == 0,
              FFMI_ERR_INVALID);
+  if ((flags & FFMI_MODEL_KV_FP8) && o->full_precision) {
+    ffmi_set_last_error("kv_fp8: fp16 models only (full_precision)", __FILE__, __LINE__);
+    return FFMI_ERR_UNSUPPORTED;
+  }
   if (flags & FFMI_MODEL_LORA) {
     // SSMs run without adapters; the fp32 model has no LoRA kernels; under TP
     // the reference shards A along F and adds before the all-reduce (not built)
@@ -71,6 +76,11 @@ extern "C" ffmi_status ffmi_model_lora_unload(ffmi_model *m, int id) {
 }
 
 extern "C" size_t ffmi_model_kv_cache_bytes(ffmi_model *m) { return m ? m->kv_cache_bytes() : 0; }
+
+extern "C" ffmi_status ffmi_model_set_kv_scales(ffmi_model *m, float k_scale, float v_scale) {
+  if (!m) return FFMI_ERR_INVALID;
+  return m->set_kv_scales(k_scale, v_scale);
+}
 
 extern "C" void ffmi_model_destroy(ffmi_model *m) { delete m; }
 

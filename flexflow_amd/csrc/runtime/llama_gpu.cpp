@@ -72,6 +72,10 @@ struct LlamaGPU : public ffmi_model {
   // their width and the qkv row [Hl | Hkv | Hkv]; otherwise K/V are (or are
   // replicated to) heads_l heads: kvh_l = heads_l, Hkv = Hl, Nqkv = 3 Hl
   bool native_gqa = false;
+  // FFMI_MODEL_KV_FP8: every layer's handle keeps an e4m3 KV cache (its steps
+  // take the two-launch attention; the o projection is never folded in)
+  bool kv_fp8 = false;
+  bool stepped = false;  // a step was staged: the kv scales are fixed
   int kvh_l = 0, Hkv = 0, Nqkv = 0;
   // GEMM inputs (normed hidden, attention output, SiLU output) are kept in
   // packed activation tiles: every GEMM then reads its activation fragments
@@ -590,7 +594,7 @@ struct LlamaGPU : public ffmi_model {
     std::vector<int> kv(o.max_requests, 0);
     for (const auto &w : ps.work) kv[w.req] = std::max(kv[w.req], w.kv_len);
     double b = 0;
-    for (int r : kv) b += (double)r * Hkv * 2 * 2;
+    for (int r : kv) b += (double)r * Hkv * 2 * (kv_fp8 ? 1 : 2);
     return b + (double)ps.tokens.size() * (Nqkv + Hl) * 2;
   }
 
@@ -607,6 +611,16 @@ struct LlamaGPU : public ffmi_model {
     size_t b = 0;
     for (const auto &L : layers) b += ffmi_attn_cache_bytes(L.attn);
     return b;
+  }
+  ffmi_status set_kv_scales(float k_scale, float v_scale) override {
+    if (!kv_fp8) return ffmi_model::set_kv_scales(k_scale, v_scale);
+    if (stepped) {
+      ffmi_set_last_error("kv_fp8: the scales are set before the model's first step", __FILE__,
+                          __LINE__);
+      return FFMI_ERR_INVALID;
+    }
+    for (auto &L : layers) TRY(ffmi::attn_set_kv_scales(L.attn, k_scale, v_scale));
+    return FFMI_OK;
   }
   long debug_width(int k) const override {
     switch (k) {
@@ -886,7 +900,7 @@ struct LlamaGPU : public ffmi_model {
                                      3 * ffmi::lora_workspace_bytes(Tm, H)}) + 3) / 4));
     }
     // (a GQA handle does not fold the o projection in: the GEMM runs)
-    fuse_ao = !native_gqa && P == 1 && d == 64 && H <= 1024 && H % 16 == 0 &&
+    fuse_ao = !native_gqa && !kv_fp8 && P == 1 && d == 64 && H <= 1024 && H % 16 == 0 &&
               !(getenv("FFMI_FUSE_AO") && atoi(getenv("FFMI_FUSE_AO")) == 0);
     if (fuse_ao) {  // decode / beam steps (<= 64 rows); prefill blocks run the GEMM
       oslab_T = std::min(Tm, 64);
@@ -1058,7 +1072,8 @@ struct LlamaGPU : public ffmi_model {
       ac.rope_high_freq_factor = c.rope_high_freq_factor;
       ac.rope_original_max_pos = c.rope_original_max_pos;
       ac.out_layout = packed ? 1 : 0;
-      TRY(ffmi_attn_create_gqa(&ac, kvh_l, &L.attn));  // (kvh_l == heads_l: ffmi_attn_create)
+      // (kvh_l == heads_l: ffmi_attn_create; no flag: ffmi_attn_create_gqa)
+      TRY(ffmi_attn_create_ex(&ac, kvh_l, kv_fp8 ? FFMI_ATTN_KV_FP8 : 0u, 1.f, 1.f, &L.attn));
       int sl = 0;
       ffmi_attn_kv_ptrs(L.attn, nullptr, nullptr, &sl);
       slots = sl;
@@ -1273,6 +1288,7 @@ struct LlamaGPU : public ffmi_model {
                  FFMI_ERR_INVALID);
     size_t bytes = 0;
     TRY(ffmi::batch_stage(b, &desc, &bytes));
+    stepped = true;
     *s = Step{b, slot, T, k, bytes};
     if (T == 0) return FFMI_OK;
     if (sampling) TRY(stage_extra(&step_u, T, b, &bytes));
@@ -1857,6 +1873,7 @@ ffmi_status create_llama_gpu(const ffmi_llama_config *cfg, const ffmi_model_opts
   m->o = *o;
   m->native_gqa = (flags & FFMI_MODEL_NATIVE_GQA) != 0;
   m->lora = (flags & FFMI_MODEL_LORA) != 0;
+  m->kv_fp8 = (flags & FFMI_MODEL_KV_FP8) != 0;
   if (m->lora && (o->mode == FFMI_MODEL_BEAM || o->tp_size > 1)) {
     delete m;
     ffmi_set_last_error("lora: INC / TREE models at tp_size 1", __FILE__, __LINE__);

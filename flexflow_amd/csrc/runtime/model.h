@@ -184,6 +184,13 @@ struct ffmi_model {
   }
   // bytes of the K plus V caches of every layer's attention handle
   virtual size_t kv_cache_bytes() const { return 0; }
+  // the k / v scales of a FFMI_MODEL_KV_FP8 model's caches, before its first step
+  virtual ffmi_status set_kv_scales(float k_scale, float v_scale) {
+    (void)k_scale, (void)v_scale;
+    ffmi_set_last_error("kv_fp8: the model was not created with FFMI_MODEL_KV_FP8", __FILE__,
+                        __LINE__);
+    return FFMI_ERR_INVALID;
+  }
   virtual long debug_width(int which) const {
     (void)which;
     return -1;

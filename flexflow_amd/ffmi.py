@@ -38,6 +38,8 @@ SPEC_EXT_WIDTH4, SPEC_EXT_MULTI_SSM = 1, 2
 # ffmi_model_create_ex flags (include/ffmi.h FFMI_MODEL_*)
 MODEL_NATIVE_GQA = 1
 MODEL_LORA = 4  # (2 is left unassigned: it stays an invalid flag)
+MODEL_KV_FP8 = 16  # (8, like 2, is left unassigned: it stays an invalid flag)
+ATTN_KV_FP8 = 1  # ffmi_attn_create_ex flag: an 8-bit (e4m3) KV cache
 LORA_MAX_ADAPTERS, LORA_MAX_RANK = 8, 64
 # FFMI_LORA_Q .. FFMI_LORA_DOWN by the HF module name (masks: 1 << id); gate_proj
 # and up_proj have ids only so that the library can refuse them
@@ -152,6 +154,9 @@ SIGNATURES = {
     "ffmi_batch_upload": (c_int, [c_void_p, ctypes.POINTER(BatchDesc), c_void_p]),
     "ffmi_attn_create": (c_int, [ctypes.POINTER(AttnCfg), ctypes.POINTER(c_void_p)]),
     "ffmi_attn_create_gqa": (c_int, [ctypes.POINTER(AttnCfg), c_int, ctypes.POINTER(c_void_p)]),
+    "ffmi_attn_create_ex": (c_int, [ctypes.POINTER(AttnCfg), c_int, ctypes.c_uint, ctypes.c_float,
+                                    ctypes.c_float, ctypes.POINTER(c_void_p)]),
+    "ffmi_model_set_kv_scales": (c_int, [c_void_p, ctypes.c_float, ctypes.c_float]),
     "ffmi_attn_cache_bytes": (c_size_t, [c_void_p]),
     "ffmi_attn_set_gqa_route": (c_int, [c_void_p, c_int]),
     "ffmi_attn_destroy": (None, [c_void_p]),
@@ -355,6 +360,16 @@ def attn_create_gqa(cfg: "AttnCfg", num_kv_heads: int) -> c_void_p:
     h = c_void_p()
     check(lib().ffmi_attn_create_gqa(ctypes.byref(cfg), num_kv_heads, ctypes.byref(h)),
           "ffmi_attn_create_gqa")
+    return h
+
+
+def attn_create_ex(cfg: "AttnCfg", num_kv_heads: int, flags: int = 0, k_scale: float = 1.0,
+                   v_scale: float = 1.0) -> c_void_p:
+    """ffmi_attn_create_ex: attn_create_gqa with flags; ATTN_KV_FP8 keeps the
+    K / V caches as e4m3 bytes of k / k_scale and v / v_scale."""
+    h = c_void_p()
+    check(lib().ffmi_attn_create_ex(ctypes.byref(cfg), num_kv_heads, flags, k_scale, v_scale,
+                                    ctypes.byref(h)), "ffmi_attn_create_ex")
     return h
 
 

@@ -36,7 +36,8 @@ class Model:
                  tp_size=1, comm=None, weights_folder: Optional[str] = None,
                  weight_init: Union[int, str] = 0, full_precision: bool = False,
                  generation_config: Optional[GenerationConfig] = None, sampling_seed: int = 0,
-                 native_gqa: bool = False, logprobs: bool = False, lora: bool = False):
+                 native_gqa: bool = False, logprobs: bool = False, lora: bool = False,
+                 kv_cache_dtype: str = "fp16", kv_scales=(1.0, 1.0)):
         """weights_folder: a checkpoint in the reference's per-tensor format
         (see checkpoint.convert_hf_model); None: seeded synthetic weights,
         `weight_init` "uniform" (0, the bench's), "depth_scaled" (1) or
@@ -48,7 +49,15 @@ class Model:
         head (FFMI_MODEL_NATIVE_GQA; fp16, num_kv_heads % tp_size == 0).
         logprobs: see set_logprobs.  lora: the model serves LoRA adapters on
         q_proj / k_proj / v_proj / o_proj and down_proj (FFMI_MODEL_LORA; see
-        load_lora): fp16 "inc" / "tree" models at tp_size 1."""
+        load_lora): fp16 "inc" / "tree" models at tp_size 1.  kv_cache_dtype
+        "fp8": the KV cache holds e4m3 bytes of k / kv_scales[0] and
+        v / kv_scales[1] (FFMI_MODEL_KV_FP8: half the cache bytes; any mode and
+        tp_size, not full_precision); "fp16" is the default model."""
+        if kv_cache_dtype not in ("fp16", "fp8"):
+            raise ValueError(f"kv_cache_dtype {kv_cache_dtype!r}: 'fp16' or 'fp8'")
+        fp8 = kv_cache_dtype == "fp8"
+        if not fp8 and tuple(kv_scales) != (1.0, 1.0):
+            raise ValueError("kv_scales apply to kv_cache_dtype='fp8' only")
         L = F.lib()
         self.config = dict(config)
         self.mode = mode
@@ -60,9 +69,13 @@ class Model:
         h = ctypes.c_void_p()
         F.check(L.ffmi_model_create_ex(ctypes.byref(cfg), ctypes.byref(opts),
                                        (F.MODEL_NATIVE_GQA if native_gqa else 0) |
-                                       (F.MODEL_LORA if lora else 0), ctypes.byref(h)),
+                                       (F.MODEL_LORA if lora else 0) |
+                                       (F.MODEL_KV_FP8 if fp8 else 0), ctypes.byref(h)),
                 "ffmi_model_create")
         self.handle = h
+        if fp8 and tuple(kv_scales) != (1.0, 1.0):
+            F.check(L.ffmi_model_set_kv_scales(h, float(kv_scales[0]), float(kv_scales[1])),
+                    "ffmi_model_set_kv_scales")
         if generation_config is not None:
             self.set_sampling(generation_config, sampling_seed)
         if logprobs:

@@ -175,6 +175,24 @@ size_t ffmi_attn_cache_bytes(ffmi_attn *h);
  * 16).  The routes give the same bits.  No effect on an MHA handle. */
 ffmi_status ffmi_attn_set_gqa_route(ffmi_attn *h, int route);
 
+/* ffmi_attn_create_gqa with flags (0: exactly that call, the scales unread).
+ *   FFMI_ATTN_KV_FP8: an 8-bit KV cache.  K8[req][kv head][slot][d] and
+ *   V8T[req][kv head][d][slot] hold one OCP e4m3fn byte per element (bias 7,
+ *   no infinities, maximum 448): byte = e4m3_rne(clamp(x / scale, -448, 448))
+ *   and stands for scale * e4m3(byte), with the static fp32 scales k_scale
+ *   and v_scale (> 0, finite; 1 keeps the values).  A NaN in k or v is outside
+ *   the contract.  ffmi_attn_inc / _spec / _tree take the handle as any other
+ *   (fp16 qkv in, fp16 out, fp16 TREE staging); ffmi_attn_kv_ptrs returns the
+ *   byte caches and ffmi_attn_cache_bytes counts 1 byte per element.  Every
+ *   step runs the KV-update launch and then the fp8-reading attention; a GQA
+ *   handle takes the kv-indexed form (ffmi_attn_set_gqa_route has no effect).
+ *   cfg->full_precision or head_dim 32: FFMI_ERR_UNSUPPORTED; a scale <= 0 or
+ *   not finite, an unknown flag: FFMI_ERR_INVALID -- "kv_fp8" in
+ *   ffmi_last_error, decided before the device is touched. */
+#define FFMI_ATTN_KV_FP8 1u
+ffmi_status ffmi_attn_create_ex(const ffmi_attn_cfg *cfg, int num_kv_heads, unsigned flags,
+                                float k_scale, float v_scale, ffmi_attn **out);
+
 /* ------------------------------------------------------------------------ */
 /* Linear (replaces Kernels::Linear::inference_kernel_wrapper,               */
 /* linear_kernels.h:54-62; cublasGemmEx at linear_kernels.cu:510-528)        */
@@ -566,6 +584,19 @@ ffmi_status ffmi_model_create_ex(const ffmi_llama_config *cfg, const ffmi_model_
 /*   (bit value 4: 2 stays an unknown flag, FFMI_ERR_INVALID, as it was before
  *   the adapters came and as callers written against that may rely on) */
 #define FFMI_MODEL_LORA 4u
+/*   FFMI_MODEL_KV_FP8: every layer's attention handle keeps an 8-bit (e4m3)
+ *   KV cache (ffmi_attn_create_ex, FFMI_ATTN_KV_FP8): half the cache bytes of
+ *   the fp16 model.  All three modes, any tp_size, with FFMI_MODEL_NATIVE_GQA
+ *   and FFMI_MODEL_LORA; full_precision: FFMI_ERR_UNSUPPORTED ("kv_fp8" in
+ *   ffmi_last_error).  Every step takes the two-launch attention, the o
+ *   projection is never folded into it, and on GQA the qkv GEMM writes fp16
+ *   rows.  ffmi_model_set_kv_scales sets the k / v scales of every layer
+ *   (default 1, 1) before the model's first step; afterwards, on a model
+ *   without the flag, or with a scale <= 0 or not finite: FFMI_ERR_INVALID.
+ *   (bit value 16: 8, like 2, stays an unknown flag, FFMI_ERR_INVALID, as it
+ *   was before this flag came and as callers written against that may rely on) */
+#define FFMI_MODEL_KV_FP8 16u
+ffmi_status ffmi_model_set_kv_scales(ffmi_model *m, float k_scale, float v_scale);
 /* LoRA adapters of a FFMI_MODEL_LORA model.  Adapter ids are process-wide
  * (0 .. FFMI_LORA_MAX_ADAPTERS - 1): a request names one at registration
  * (ffmi_rm_register_request_ex) and the model that loaded it serves it.
@@ -1026,7 +1057,9 @@ const char *ffmi_last_error(void);
  * down_proj: FFMI_MODEL_LORA, ffmi_model_lora_load(_folder) / _unload,
  * ffmi_lora_apply(_workspace_bytes), ffmi_rm_register_request_ex; and on the
  * attention projections: ffmi_model_lora_load_modules, _load_folder_ex,
- * ffmi_lora_apply_qkv, ffmi_lora_qkv_workspace_bytes */
+ * ffmi_lora_apply_qkv, ffmi_lora_qkv_workspace_bytes; and the 8-bit KV cache:
+ * ffmi_attn_create_ex (FFMI_ATTN_KV_FP8), FFMI_MODEL_KV_FP8,
+ * ffmi_model_set_kv_scales */
 const char *ffmi_version(void);
 
 #ifdef __cplusplus
