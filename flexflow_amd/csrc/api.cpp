@@ -676,6 +676,91 @@ extern "C" ffmi_status ffmi_linear(const void *X, const void *W_packed, void *Y,
   return ffmi_linear_ws(X, W_packed, Y, T, out_dim, in_dim, epilogue, ws, g_ws_bytes, stream);
 }
 
+// fp8 (e4m3) weight-only linear layers (kernels/gemm_w8.hip)
+static ffmi_status w8_refuse(ffmi_status code, const char *why, int line) {
+  ffmi_set_last_error(why, __FILE__, line);
+  return code;
+}
+#define FFMI_W8_CHECK(cond, code, why) \
+  do { if (!(cond)) return w8_refuse((code), "w8: " why, __LINE__); } while (0)
+
+extern "C" size_t ffmi_linear_w8_packed_bytes(int out_dim, int in_dim) {
+  if (out_dim <= 0 || in_dim <= 0 || in_dim % 64) return 0;
+  return ffmi::w8_packed_bytes(out_dim, in_dim);
+}
+
+extern "C" size_t ffmi_linear_w8_scale_count(int out_dim) {
+  return out_dim > 0 ? (size_t)(out_dim + 15) / 16 * 16 : 0;
+}
+
+extern "C" ffmi_status ffmi_linear_w8_quantize_pack(const void *W_f16, int out_dim, int in_dim,
+                                                    void *W8_packed, float *scales,
+                                                    ffmi_stream stream) {
+  FFMI_W8_CHECK(W_f16 && W8_packed && scales && out_dim > 0 && in_dim > 0, FFMI_ERR_INVALID,
+                "null pointer or empty matrix");
+  FFMI_W8_CHECK(in_dim % 64 == 0, FFMI_ERR_UNSUPPORTED, "in_dim % 64 != 0");
+  FFMI_HIP(ffmi::launch_w8_quantize_pack((const uint16_t *)W_f16, in_dim, out_dim, in_dim,
+                                         (uint8_t *)W8_packed, scales, 1, 0, (out_dim + 15) / 16,
+                                         (hipStream_t)stream));
+  return FFMI_OK;
+}
+
+extern "C" ffmi_status ffmi_linear_w8_quantize_pack_gate_up(const void *Wg_f16, const void *Wu_f16,
+                                                            int out_dim, int in_dim,
+                                                            void *W8_packed, float *scales,
+                                                            ffmi_stream stream) {
+  FFMI_W8_CHECK(Wg_f16 && Wu_f16 && W8_packed && scales && out_dim > 0 && in_dim > 0,
+                FFMI_ERR_INVALID, "null pointer or empty matrix");
+  FFMI_W8_CHECK(in_dim % 64 == 0, FFMI_ERR_UNSUPPORTED, "in_dim % 64 != 0");
+  const int pitch = 2 * ((out_dim + 15) / 16);
+  FFMI_HIP(ffmi::launch_w8_quantize_pack((const uint16_t *)Wg_f16, in_dim, out_dim, in_dim,
+                                         (uint8_t *)W8_packed, scales, 2, 0, pitch,
+                                         (hipStream_t)stream));
+  FFMI_HIP(ffmi::launch_w8_quantize_pack((const uint16_t *)Wu_f16, in_dim, out_dim, in_dim,
+                                         (uint8_t *)W8_packed, scales, 2, 1, pitch,
+                                         (hipStream_t)stream));
+  return FFMI_OK;
+}
+
+extern "C" size_t ffmi_linear_w8_workspace_bytes(int T, int out_dim, int in_dim, int epilogue) {
+  return ffmi::gemm_w8_workspace_bytes(T, out_dim, in_dim, epilogue);
+}
+
+extern "C" ffmi_status ffmi_linear_w8(const void *X, const void *W8_packed, const float *scales,
+                                      void *Y, int T, int out_dim, int in_dim, int epilogue,
+                                      void *workspace, size_t workspace_bytes,
+                                      ffmi_stream stream) {
+  FFMI_W8_CHECK(X && W8_packed && scales && Y, FFMI_ERR_INVALID, "null pointer");
+  FFMI_W8_CHECK(T >= 0 && out_dim > 0 && in_dim > 0, FFMI_ERR_INVALID, "T < 0 or an empty matrix");
+  FFMI_W8_CHECK(in_dim % 64 == 0, FFMI_ERR_UNSUPPORTED, "in_dim % 64 != 0");
+  FFMI_W8_CHECK(!(epilogue & (FFMI_X_PACKED | FFMI_Y_PACKED)), FFMI_ERR_UNSUPPORTED,
+                "row-major activations only (FFMI_X_PACKED / FFMI_Y_PACKED)");
+  const int base = epilogue & ~FFMI_W_STREAM;
+  FFMI_W8_CHECK(base == FFMI_EPI_NONE || base == FFMI_EPI_SILU_MUL, FFMI_ERR_INVALID,
+                "unknown epilogue");
+  FFMI_W8_CHECK(workspace_bytes >= ffmi::gemm_w8_workspace_bytes(T, out_dim, in_dim, epilogue) &&
+                    (workspace || !ffmi::gemm_w8_workspace_bytes(T, out_dim, in_dim, epilogue)),
+                FFMI_ERR_INVALID, "workspace smaller than ffmi_linear_w8_workspace_bytes");
+  FFMI_HIP(ffmi::launch_gemm_w8((const uint16_t *)X, (const uint8_t *)W8_packed, scales,
+                                (uint16_t *)Y, (float *)workspace, workspace_bytes, T, out_dim,
+                                in_dim, epilogue, (hipStream_t)stream));
+  return FFMI_OK;
+}
+
+extern "C" ffmi_status ffmi_debug_linear_w8_unpack(const void *W8_packed, int out_dim, int in_dim,
+                                                   int gate_up, void *bytes_out,
+                                                   ffmi_stream stream) {
+  FFMI_W8_CHECK(W8_packed && bytes_out && out_dim > 0 && in_dim > 0, FFMI_ERR_INVALID,
+                "null pointer or empty matrix");
+  FFMI_W8_CHECK(in_dim % 64 == 0, FFMI_ERR_UNSUPPORTED, "in_dim % 64 != 0");
+  FFMI_W8_CHECK(gate_up >= 0 && gate_up <= 2, FFMI_ERR_INVALID, "gate_up: 0, 1 (gate) or 2 (up)");
+  const int nt = (out_dim + 15) / 16;
+  FFMI_HIP(ffmi::launch_w8_unpack((const uint8_t *)W8_packed, out_dim, in_dim,
+                                  (uint8_t *)bytes_out, gate_up ? 2 : 1, gate_up == 2 ? 1 : 0,
+                                  gate_up ? 2 * nt : nt, (hipStream_t)stream));
+  return FFMI_OK;
+}
+
 extern "C" ffmi_status ffmi_rmsnorm(const void *x, const void *w, void *out, int T, int H,
                                     float eps, ffmi_stream stream) {
   FFMI_CHECK(x && w && out && H % 8 == 0 && H <= 16384, FFMI_ERR_INVALID);

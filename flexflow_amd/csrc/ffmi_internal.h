@@ -45,6 +45,16 @@ __device__ __forceinline__ h8 ld_weight(const uint16_t *p) {
   else return *reinterpret_cast<const h8 *>(p);
 }
 
+// (gemm.hip, gemm_w8.hip) SigmoidSiluMultiKernel numerics (sigmoid_silu_multi.cu:41-46): gate and up
+// are fp16 values, out = half(half(g * half(sigmoid(g))) * u)
+__device__ __forceinline__ uint16_t silu_mul_h(float gacc, float uacc) {
+  const float g = __half2float(__float2half_rn(gacc));
+  const float u = __half2float(__float2half_rn(uacc));
+  const float sg = __half2float(__float2half_rn(1.0f / (1.0f + expf(-g))));
+  const float t = __half2float(__float2half_rn(g * sg));
+  return __half_as_ushort(__float2half_rn(t * u));
+}
+
 // Packed activation tiles (FFMI_X_PACKED / FFMI_Y_PACKED): element (m, n) of a
 // [T][K] activation lives at [m/16][n/32][lane = (m&15) + 16*((n>>3)&3)][n&7],
 // i.e. each 16-row x 32-column block is one MFMA operand fragment (1 KiB,
@@ -340,6 +350,28 @@ hipError_t launch_attention_fp8(const char *blob, int W, int max_q, const uint16
                                 const uint8_t *kc, const uint8_t *vc, uint16_t *out, int heads,
                                 int d, int slots, float scale, float k_scale, float v_scale,
                                 bool out_packed, int kv_heads, hipStream_t s);
+
+// kernels/gemm_w8.hip: fp8 (e4m3) weight-only linear layers.  W8: 1 KiB double
+// blocks (16 rows x 64 k, K-major, `pitch` tiles per k-row), scales: one fp32
+// per output channel, padded to 16.  plan_w8 depends on (N, K, epilogue) only.
+struct W8Plan {
+  int ntiles = 0, nblk = 0, KT2 = 0, S = 1;  // 16-column tiles, tile groups, k/64, k-slices
+};
+W8Plan plan_w8(int N, int K, int epilogue);
+size_t w8_packed_bytes(int N, int K);
+size_t gemm_w8_workspace_bytes(int T, int N, int K, int epilogue);
+// rows [0, N) of a row-major fp16 matrix (row stride ld) -> destination tiles
+// tile_step * nt + tile_offset and their scales[16 * tile + row]
+hipError_t launch_w8_quantize_pack(const uint16_t *src, int ld, int N, int K, uint8_t *dst,
+                                   float *scales, int tile_step, int tile_offset, int pitch,
+                                   hipStream_t s);
+hipError_t launch_w8_unpack(const uint8_t *src, int N, int K, uint8_t *dst, int tile_step,
+                            int tile_offset, int pitch, hipStream_t s);
+// Y [T][N] fp16 rows = s[n] * (X [T][K] . q^T), epilogue FFMI_EPI_NONE /
+// FFMI_EPI_SILU_MUL (| FFMI_W_STREAM); any T (blocks of 64 rows)
+hipError_t launch_gemm_w8(const uint16_t *X, const uint8_t *W8, const float *scales, uint16_t *Y,
+                          float *ws, size_t ws_bytes, int T, int N, int K, int epilogue,
+                          hipStream_t s);
 
 uint64_t weight_key(const char *name, uint64_t seed);
 

@@ -40,16 +40,6 @@ __device__ __forceinline__ void static_for(F &&f) {
   static_for_impl<0, N>(f);
 }
 
-// SigmoidSiluMultiKernel numerics (sigmoid_silu_multi.cu:41-46): gate and up
-// are fp16 values, out = half(half(g * half(sigmoid(g))) * u)
-__device__ __forceinline__ uint16_t silu_mul_h(float gacc, float uacc) {
-  const float g = __half2float(__float2half_rn(gacc));
-  const float u = __half2float(__float2half_rn(uacc));
-  const float sg = __half2float(__float2half_rn(1.0f / (1.0f + expf(-g))));
-  const float t = __half2float(__float2half_rn(g * sg));
-  return __half_as_ushort(__float2half_rn(t * u));
-}
-
 // Split-K over workgroups (grid.y = S > 1, small-N layers only): each
 // workgroup reduces its K slice over its waves and writes an fp32 partial
 // slab [S][T][NTILES*16] that the consumer combines in slice order

@@ -21,8 +21,21 @@ extern "C" ffmi_status ffmi_model_create_ex(const ffmi_llama_config *cfg, const 
                                             unsigned flags, ffmi_model **out) {
   if (!flags) return ffmi_model_create(cfg, o, out);
   FFMI_CHECK(cfg && o && out &&
-                 (flags & ~(FFMI_MODEL_NATIVE_GQA | FFMI_MODEL_LORA | FFMI_MODEL_KV_FP8)) == 0,
+                 (flags & ~(FFMI_MODEL_NATIVE_GQA | FFMI_MODEL_LORA | FFMI_MODEL_KV_FP8 |
+                            FFMI_MODEL_W8)) == 0,
              FFMI_ERR_INVALID);
+  if (flags & FFMI_MODEL_W8) {
+    // the fp32 model has no fp8 GEMM; sharded scales and the all-reduce forms,
+    // and the LoRA routes on top of the w8 route, are not built
+    const char *why = o->full_precision            ? "w8: fp16 models only (full_precision)"
+                      : o->tp_size > 1             ? "w8: tp_size > 1"
+                      : (flags & FFMI_MODEL_LORA)  ? "w8: LoRA adapters on fp8 weights are not served"
+                                                   : nullptr;
+    if (why) {
+      ffmi_set_last_error(why, __FILE__, __LINE__);
+      return FFMI_ERR_UNSUPPORTED;
+    }
+  }
   if ((flags & FFMI_MODEL_KV_FP8) && o->full_precision) {
     ffmi_set_last_error("kv_fp8: fp16 models only (full_precision)", __FILE__, __LINE__);
     return FFMI_ERR_UNSUPPORTED;
@@ -76,6 +89,8 @@ extern "C" ffmi_status ffmi_model_lora_unload(ffmi_model *m, int id) {
 }
 
 extern "C" size_t ffmi_model_kv_cache_bytes(ffmi_model *m) { return m ? m->kv_cache_bytes() : 0; }
+
+extern "C" size_t ffmi_model_weight_bytes(ffmi_model *m) { return m ? m->weight_bytes() : 0; }
 
 extern "C" ffmi_status ffmi_model_set_kv_scales(ffmi_model *m, float k_scale, float v_scale) {
   if (!m) return FFMI_ERR_INVALID;

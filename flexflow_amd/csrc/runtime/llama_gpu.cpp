@@ -39,6 +39,9 @@ namespace {
 struct Layer {
   uint16_t *in_norm = nullptr, *post_norm = nullptr;
   uint16_t *wqkv = nullptr, *wo = nullptr, *wgu = nullptr, *wd = nullptr;
+  // FFMI_MODEL_W8: e4m3 bytes and per-channel scales instead of the four above
+  uint8_t *qkv8 = nullptr, *o8 = nullptr, *gu8 = nullptr, *d8 = nullptr;
+  float *qkv_s = nullptr, *o_s = nullptr, *gu_s = nullptr, *d_s = nullptr;
   ffmi_attn *attn = nullptr;
 };
 
@@ -76,6 +79,16 @@ struct LlamaGPU : public ffmi_model {
   // take the two-launch attention; the o projection is never folded in)
   bool kv_fp8 = false;
   bool stepped = false;  // a step was staged: the kv scales are fixed
+  // FFMI_MODEL_W8: the linear layers hold fp8 (e4m3) bytes and per-channel
+  // scales (kernels/gemm_w8.hip).  Every norm of a step is a launch and every
+  // GEMM launch_gemm_w8 writing fp16 rows -- the shape of the route LoRA steps
+  // take: no fused residual norms, no deferred slabs, no folded o projection,
+  // row-major activations (packed = false)
+  bool w8 = false;
+  uint8_t *lm8 = nullptr;
+  float *lm_s = nullptr;
+  size_t wbytes = 0;  // resident bytes of the linear-layer weights
+  size_t weight_bytes() const override { return wbytes; }
   int kvh_l = 0, Hkv = 0, Nqkv = 0;
   // GEMM inputs (normed hidden, attention output, SiLU output) are kept in
   // packed activation tiles: every GEMM then reads its activation fragments
@@ -586,8 +599,8 @@ struct LlamaGPU : public ffmi_model {
     }
     return n;
   }
-  static double gemm_bytes(int T, int N_w, int N_out, int K) {
-    return 2.0 * ((double)N_w * K + (double)T * K + (double)T * N_out);
+  double gemm_bytes(int T, int N_w, int N_out, int K) const {
+    return (w8 ? 1.0 : 2.0) * N_w * K + 2.0 * ((double)T * K + (double)T * N_out);
   }
   double attn_bytes() const {
     // K and V of every visible slot of each request read once + qkv in + out
@@ -734,6 +747,7 @@ struct LlamaGPU : public ffmi_model {
     // (non-blocking) stream first in every branch
     if (stream) FFMI_HIP(hipStreamSynchronize(stream));
     if (kind == FFMI_FAULT_TP_HEAD_SWAP) {
+      if (w8) return refuse("w8: the head-swap fault repacks fp16 weights");
       FFMI_CHECK(layer >= -1 && layer < c.num_layers && heads_l >= 2 && d % 16 == 0,
                  FFMI_ERR_INVALID);
       for (int l = 0; l < c.num_layers; ++l)
@@ -872,13 +886,16 @@ struct LlamaGPU : public ffmi_model {
     }
     Fl = F / P;
     FFMI_CHECK(H % 32 == 0 && Hl % 32 == 0 && Fl % 32 == 0, FFMI_ERR_UNSUPPORTED);
+    if (w8 && (P > 1 || lora)) return refuse("w8: tp_size 1, without LoRA adapters");
+    if (w8 && (H % 64 || Hl % 64 || Fl % 64))
+      return refuse("w8: hidden, heads * head_dim and intermediate must be multiples of 64");
     FFMI_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
     Tm = (o.max_tokens + 15) & ~15;
-    packed = H % 32 == 0 && Hl % 32 == 0 && Fl % 32 == 0;
+    packed = !w8 && H % 32 == 0 && Hl % 32 == 0 && Fl % 32 == 0;
     {
-      const double wbytes = 2.0 * c.num_layers * (((double)Nqkv + Hl) * H + 3.0 * Fl * H) +
-                            2.0 * V * H;
-      wstream = wbytes > 192.0 * (1 << 20) ? FFMI_W_STREAM : 0;
+      const double streamed = (w8 ? 1.0 : 2.0) *
+                              (c.num_layers * (((double)Nqkv + Hl) * H + 3.0 * Fl * H) + (double)V * H);
+      wstream = streamed > 192.0 * (1 << 20) ? FFMI_W_STREAM : 0;
       if (const char *e = getenv("FFMI_W_STREAM"))  // A/B override: 0 / 1
         wstream = atoi(e) ? FFMI_W_STREAM : 0;
     }
@@ -900,7 +917,7 @@ struct LlamaGPU : public ffmi_model {
                                      3 * ffmi::lora_workspace_bytes(Tm, H)}) + 3) / 4));
     }
     // (a GQA handle does not fold the o projection in: the GEMM runs)
-    fuse_ao = !native_gqa && !kv_fp8 && P == 1 && d == 64 && H <= 1024 && H % 16 == 0 &&
+    fuse_ao = !native_gqa && !kv_fp8 && !w8 && P == 1 && d == 64 && H <= 1024 && H % 16 == 0 &&
               !(getenv("FFMI_FUSE_AO") && atoi(getenv("FFMI_FUSE_AO")) == 0);
     if (fuse_ao) {  // decode / beam steps (<= 64 rows); prefill blocks run the GEMM
       oslab_T = std::min(Tm, 64);
@@ -942,7 +959,13 @@ struct LlamaGPU : public ffmi_model {
     {
       // the split-K factor depends on the row-block count, so take the max
       // over every batch size the model can see
-      for (int t = 16; t <= Tm; t += 16) {
+      // (w8: the plan does not depend on T; a launch covers at most 64 rows)
+      if (w8)
+        ws_bytes = std::max({ffmi::gemm_w8_workspace_bytes(Tm, Nqkv, H, 0),
+                             ffmi::gemm_w8_workspace_bytes(Tm, H, Hl, 0),
+                             ffmi::gemm_w8_workspace_bytes(Tm, H, Fl, 0),
+                             ffmi::gemm_w8_workspace_bytes(Tm, Vl, H, 0)});
+      for (int t = 16; t <= Tm && !w8; t += 16) {
         const size_t w1 = ffmi_linear_workspace_bytes(t, Nqkv, H, FFMI_EPI_NONE);
         const size_t w2 = ffmi_linear_workspace_bytes(t, H, Hl, FFMI_EPI_NONE);
         const size_t w3 = ffmi_linear_workspace_bytes(t, Fl, H, FFMI_EPI_SILU_MUL);
@@ -997,6 +1020,26 @@ struct LlamaGPU : public ffmi_model {
                                         stream, cols, pa, 17, scale));
       return FFMI_OK;
     };
+    // a linear weight of `ntiles` 16-row tiles: packed fp16, or (w8) bytes and
+    // scales quantised straight from the row-major staging -- the fp16 tiles
+    // are never made
+    auto linear_alloc = [&](uint16_t **w16, uint8_t **q8, float **sc, int ntiles, int K) -> ffmi_status {
+      if (!w8) {
+        wbytes += (size_t)ntiles * ((K + 31) / 32) * 1024;
+        return alloc(w16, (size_t)ntiles * ((K + 31) / 32) * 512);
+      }
+      wbytes += (size_t)ntiles * (K / 64) * 1024 + (size_t)ntiles * 16 * sizeof(float);
+      TRY(alloc(q8, (size_t)ntiles * (K / 64) * 1024));
+      return alloc(sc, (size_t)ntiles * 16);
+    };
+    auto linear_pack = [&](const uint16_t *src, int ld, int row0, int col0, int N, int K,
+                           uint16_t *w16, uint8_t *q8, float *sc, int step, int off,
+                           int pitch) -> hipError_t {
+      if (w8)  // (tp_size 1: row0 = col0 = 0)
+        return ffmi::launch_w8_quantize_pack(src + (size_t)row0 * ld + col0, ld, N, K, q8, sc, step,
+                                             off, pitch, stream);
+      return launch_pack_weight(src, ld, row0, col0, N, K, w16, step, off, pitch, stream);
+    };
     const bool chain = o.weight_init == 2 && weights_folder.empty();
     float chain_scale = 128.0f;
     for (long long f2 = 1; f2 * 32LL * (4096 + 2 * 11008) <
@@ -1007,14 +1050,14 @@ struct LlamaGPU : public ffmi_model {
     TRY(fill(embed, (size_t)V * H, "model.embed_tokens.weight", 0, 0, 1, chain ? chain_scale : 1.0f));
     TRY(alloc(&final_norm, H));
     TRY(fill(final_norm, H, "model.norm.weight", 1));
-    TRY(alloc(&lm, ffmi_linear_packed_bytes(Vl, H) / 2));
+    TRY(linear_alloc(&lm, &lm8, &lm_s, (Vl + 15) / 16, H));
     if (chain)
       TRY(fill(tmp, (size_t)V * H, "model.embed_tokens.weight", 0, H, 7919));
     else
       TRY(fill(tmp, (size_t)V * H, "lm_head.weight", 0));
     // vocab shard s: rows [s*Vl, (s+1)*Vl) (the whole table when replicated)
-    FFMI_HIP(launch_pack_weight(tmp, H, Vl == V ? 0 : o.tp_rank * Vl, 0, Vl, H, lm, 1, 0,
-                                (Vl + 15) / 16, stream));
+    FFMI_HIP(linear_pack(tmp, H, Vl == V ? 0 : o.tp_rank * Vl, 0, Vl, H, lm, lm8, lm_s, 1, 0,
+                         (Vl + 15) / 16));
     slots = 0;
     layers.resize(c.num_layers);
     const int s = o.tp_rank;
@@ -1026,7 +1069,7 @@ struct LlamaGPU : public ffmi_model {
       TRY(alloc(&L.post_norm, H));
       TRY(fill(L.post_norm, H, p + "post_attention_layernorm.weight", 1));
       // qkv: [Q_s | K_s | V_s] rows of this shard (file_loader.cc:286-303)
-      TRY(alloc(&L.wqkv, ffmi_linear_packed_bytes(Nqkv, H) / 2));
+      TRY(linear_alloc(&L.wqkv, &L.qkv8, &L.qkv_s, Nqkv / 16, H));
       const char *names[3] = {"self_attn.q_proj.weight", "self_attn.k_proj.weight",
                               "self_attn.v_proj.weight"};
       for (int q = 0; q < 3; ++q) {
@@ -1036,25 +1079,25 @@ struct LlamaGPU : public ffmi_model {
         const int Nl = q > 0 ? Hkv : Hl;  // this rank's rows of the tensor
         TRY(fill(tmp, rows * H, p + names[q], 0));
         // one allocation of Nqkv / 16 tiles per k-row: Q, K, V tiles side by side
-        FFMI_HIP(launch_pack_weight(tmp, H, s * Nl, 0, Nl, H, L.wqkv, 1,
-                                    (q > 0 ? Hl + (q - 1) * Hkv : 0) / 16, Nqkv / 16, stream));
+        FFMI_HIP(linear_pack(tmp, H, s * Nl, 0, Nl, H, L.wqkv, L.qkv8, L.qkv_s, 1,
+                             (q > 0 ? Hl + (q - 1) * Hkv : 0) / 16, Nqkv / 16));
       }
       // o_proj: row-parallel -> columns [s*Hl, (s+1)*Hl)
-      TRY(alloc(&L.wo, ffmi_linear_packed_bytes(H, Hl) / 2));
+      TRY(linear_alloc(&L.wo, &L.o8, &L.o_s, H / 16, Hl));
       TRY(fill(tmp, (size_t)H * H, p + "self_attn.o_proj.weight", kres));
-      FFMI_HIP(launch_pack_weight(tmp, H, 0, s * Hl, H, Hl, L.wo, 1, 0, H / 16, stream));
+      FFMI_HIP(linear_pack(tmp, H, 0, s * Hl, H, Hl, L.wo, L.o8, L.o_s, 1, 0, H / 16));
       // gate | up: column-parallel, interleaved 16-column tiles
-      TRY(alloc(&L.wgu, 2 * ffmi_linear_packed_bytes(Fl, H) / 2));
+      TRY(linear_alloc(&L.wgu, &L.gu8, &L.gu_s, 2 * ((Fl + 15) / 16), H));
       TRY(fill(tmp, (size_t)F * H, p + "mlp.gate_proj.weight", 0));
-      FFMI_HIP(launch_pack_weight(tmp, H, s * Fl, 0, Fl, H, L.wgu, 2, 0, 2 * ((Fl + 15) / 16),
-                                  stream));
+      FFMI_HIP(linear_pack(tmp, H, s * Fl, 0, Fl, H, L.wgu, L.gu8, L.gu_s, 2, 0,
+                           2 * ((Fl + 15) / 16)));
       TRY(fill(tmp, (size_t)F * H, p + "mlp.up_proj.weight", 0));
-      FFMI_HIP(launch_pack_weight(tmp, H, s * Fl, 0, Fl, H, L.wgu, 2, 1, 2 * ((Fl + 15) / 16),
-                                  stream));
+      FFMI_HIP(linear_pack(tmp, H, s * Fl, 0, Fl, H, L.wgu, L.gu8, L.gu_s, 2, 1,
+                           2 * ((Fl + 15) / 16)));
       // down: row-parallel -> columns [s*Fl, (s+1)*Fl) of [H][F]
-      TRY(alloc(&L.wd, ffmi_linear_packed_bytes(H, Fl) / 2));
+      TRY(linear_alloc(&L.wd, &L.d8, &L.d_s, H / 16, Fl));
       TRY(fill(tmp, (size_t)H * F, p + "mlp.down_proj.weight", kres));
-      FFMI_HIP(launch_pack_weight(tmp, F, 0, s * Fl, H, Fl, L.wd, 1, 0, H / 16, stream));
+      FFMI_HIP(linear_pack(tmp, F, 0, s * Fl, H, Fl, L.wd, L.d8, L.d_s, 1, 0, H / 16));
       ffmi_attn_cfg ac{};  // (zeroed: fields added to the ABI later default to 0)
       ac.mode = mode == FFMI_MODEL_TREE ? FFMI_ATTN_TREE
                                         : (mode == FFMI_MODEL_BEAM ? FFMI_ATTN_SPEC : FFMI_ATTN_INC);
@@ -1428,7 +1471,7 @@ struct LlamaGPU : public ffmi_model {
     static const int marker_h = getenv("FFMI_MARKERS") ? atoi(getenv("FFMI_MARKERS")) : 0;
     static const int marker_t = getenv("FFMI_MARKERS_T") ? atoi(getenv("FFMI_MARKERS_T")) : 0;
     int mark_i = 0;
-    const bool fuse = (fuse_norms == 2 || (fuse_norms == 1 && H >= 2048)) && !dbg &&
+    const bool fuse = (fuse_norms == 2 || (fuse_norms == 1 && H >= 2048)) && !dbg && !w8 &&
                       o.tp_size == 1 && T <= 32 && H % 32 == 0 && Hl % 32 == 0 && H <= 4096;
     // (FFMI_MODEL_LORA, the modules of the step's route, lora_route.  down: it
     // runs unfused and its split-K slabs are reduced into proj for the update,
@@ -1447,6 +1490,13 @@ struct LlamaGPU : public ffmi_model {
     const int32_t *const lslots =
         lora ? reinterpret_cast<const int32_t *>(step.batch->dev + step_slots.off) : nullptr;
     // the residual norms inside the transport's all-reduces (tp_fuse_norm)
+    // (FFMI_MODEL_W8: fuse, fuse_ao, lora and arn are all off, so a step takes
+    // the norm launches and the plain GEMM sites below, each of them gemm8)
+    auto gemm8 = [&](const uint16_t *X, const uint8_t *W, const float *sc, uint16_t *Y, int N, int K,
+                     int epi) -> ffmi_status {
+      FFMI_HIP(ffmi::launch_gemm_w8(X, W, sc, Y, ws, ws_bytes, T, N, K, epi | wstream, stream));
+      return FFMI_OK;
+    };
     const bool arn = peer && !solo && o.tp_size > 1 && (tp_fuse_norm == 2 || (tp_fuse_norm == 1 && !dbg));
     for (int l = 0; l < c.num_layers; ++l) {
       Layer &L = layers[l];
@@ -1507,6 +1557,8 @@ struct LlamaGPU : public ffmi_model {
       pr = prof_begin(on);
       ffmi::Partials qkv_part;
       // (a GQA handle takes fp16 qkv rows: a split-K plan runs its reduce pass)
+      if (w8) TRY(gemm8(h, L.qkv8, L.qkv_s, qkv, Nqkv, H, FFMI_EPI_NONE));
+      else
       FFMI_HIP(ffmi::launch_gemm(fz_in ? res : h, L.wqkv, qkv, (float *)ws, ws_bytes, T, Nqkv, H,
                                  fz_in ? wstream : XP, stream,
                                  native_gqa || lora_qkv ? nullptr : &qkv_part, 0,
@@ -1546,6 +1598,8 @@ struct LlamaGPU : public ffmi_model {
         mk();
       } else if (o.tp_size == 1 || solo) {
         pr = prof_begin(on);
+        if (w8) TRY(gemm8(att, L.o8, L.o_s, proj, H, Hl, FFMI_EPI_NONE));
+        else
         FFMI_HIP(ffmi::launch_gemm(att, L.wo, proj, (float *)ws, ws_bytes, T, H, Hl, XP, stream,
                                    H <= 8192 ? &o_part : nullptr));
         prof_end(pr, GEMM_O, gemm_bytes(T, H, H, Hl), 2.0 * T * H * Hl);
@@ -1583,7 +1637,9 @@ struct LlamaGPU : public ffmi_model {
       if (dbg) TRY(dbg_copy(FFMI_DBG_FFN_NORM, l, h, T));
       pr = prof_begin(on);
       const int YP = packed ? FFMI_Y_PACKED : 0;
-      if (fuse_o)
+      if (w8)
+        TRY(gemm8(h, L.gu8, L.gu_s, mlp, Fl, H, FFMI_EPI_SILU_MUL));
+      else if (fuse_o)
         FFMI_HIP(ffmi::launch_gemm(res, L.wgu, mlp, (float *)ws, ws_bytes, T, Fl, H,
                                    FFMI_EPI_SILU_MUL | YP | wstream, stream, nullptr, 0, &fz_gu));
       else
@@ -1600,6 +1656,8 @@ struct LlamaGPU : public ffmi_model {
         mk();
       } else if (o.tp_size == 1 || solo) {
         pr = prof_begin(on);
+        if (w8) TRY(gemm8(mlp, L.d8, L.d_s, proj, H, Fl, FFMI_EPI_NONE));
+        else
         FFMI_HIP(ffmi::launch_gemm(mlp, L.wd, proj, (float *)ws, ws_bytes, T, H, Fl, XP, stream,
                                    H <= 8192 ? &down_part : nullptr));
         prof_end(pr, GEMM_DOWN, gemm_bytes(T, H, H, Fl), 2.0 * T * H * Fl);
@@ -1655,7 +1713,8 @@ struct LlamaGPU : public ffmi_model {
       dbg_T = T;
     }
     pr = prof_begin(ptail);
-    TRY(ffmi_linear_ws(h, lm, logits, T, Vl, H, FFMI_EPI_NONE | XP, ws, ws_bytes, s));
+    if (w8) TRY(gemm8(h, lm8, lm_s, logits, Vl, H, FFMI_EPI_NONE));
+    else TRY(ffmi_linear_ws(h, lm, logits, T, Vl, H, FFMI_EPI_NONE | XP, ws, ws_bytes, s));
     prof_end(pr, GEMM_LM_HEAD, gemm_bytes(T, Vl, Vl, H), 2.0 * T * Vl * H);
     mkt();
     pr = prof_begin(ptail);
@@ -1874,6 +1933,7 @@ ffmi_status create_llama_gpu(const ffmi_llama_config *cfg, const ffmi_model_opts
   m->native_gqa = (flags & FFMI_MODEL_NATIVE_GQA) != 0;
   m->lora = (flags & FFMI_MODEL_LORA) != 0;
   m->kv_fp8 = (flags & FFMI_MODEL_KV_FP8) != 0;
+  m->w8 = (flags & FFMI_MODEL_W8) != 0;
   if (m->lora && (o->mode == FFMI_MODEL_BEAM || o->tp_size > 1)) {
     delete m;
     ffmi_set_last_error("lora: INC / TREE models at tp_size 1", __FILE__, __LINE__);

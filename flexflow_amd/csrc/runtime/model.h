@@ -184,6 +184,8 @@ struct ffmi_model {
   }
   // bytes of the K plus V caches of every layer's attention handle
   virtual size_t kv_cache_bytes() const { return 0; }
+  // resident bytes of the linear-layer weights (ffmi_model_weight_bytes)
+  virtual size_t weight_bytes() const { return 0; }
   // the k / v scales of a FFMI_MODEL_KV_FP8 model's caches, before its first step
   virtual ffmi_status set_kv_scales(float k_scale, float v_scale) {
     (void)k_scale, (void)v_scale;

@@ -37,7 +37,7 @@ class Model:
                  weight_init: Union[int, str] = 0, full_precision: bool = False,
                  generation_config: Optional[GenerationConfig] = None, sampling_seed: int = 0,
                  native_gqa: bool = False, logprobs: bool = False, lora: bool = False,
-                 kv_cache_dtype: str = "fp16", kv_scales=(1.0, 1.0)):
+                 kv_cache_dtype: str = "fp16", kv_scales=(1.0, 1.0), weight_dtype: str = "fp16"):
         """weights_folder: a checkpoint in the reference's per-tensor format
         (see checkpoint.convert_hf_model); None: seeded synthetic weights,
         `weight_init` "uniform" (0, the bench's), "depth_scaled" (1) or
@@ -52,7 +52,14 @@ class Model:
         load_lora): fp16 "inc" / "tree" models at tp_size 1.  kv_cache_dtype
         "fp8": the KV cache holds e4m3 bytes of k / kv_scales[0] and
         v / kv_scales[1] (FFMI_MODEL_KV_FP8: half the cache bytes; any mode and
-        tp_size, not full_precision); "fp16" is the default model."""
+        tp_size, not full_precision); "fp16" is the default model.
+        weight_dtype "fp8": the linear layers (q/k/v, o, gate/up, down, lm_head)
+        keep e4m3 bytes with one fp32 scale per output channel and run the
+        fp8-weight GEMM (FFMI_MODEL_W8: about half the weight bytes, see
+        weight_bytes; any mode, with native_gqa and kv_cache_dtype="fp8"; not
+        full_precision, tp_size > 1 or lora); "fp16" is the default model."""
+        if weight_dtype not in ("fp16", "fp8"):
+            raise ValueError(f"weight_dtype {weight_dtype!r}: 'fp16' or 'fp8'")
         if kv_cache_dtype not in ("fp16", "fp8"):
             raise ValueError(f"kv_cache_dtype {kv_cache_dtype!r}: 'fp16' or 'fp8'")
         fp8 = kv_cache_dtype == "fp8"
@@ -70,7 +77,8 @@ class Model:
         F.check(L.ffmi_model_create_ex(ctypes.byref(cfg), ctypes.byref(opts),
                                        (F.MODEL_NATIVE_GQA if native_gqa else 0) |
                                        (F.MODEL_LORA if lora else 0) |
-                                       (F.MODEL_KV_FP8 if fp8 else 0), ctypes.byref(h)),
+                                       (F.MODEL_KV_FP8 if fp8 else 0) |
+                                       (F.MODEL_W8 if weight_dtype == "fp8" else 0), ctypes.byref(h)),
                 "ffmi_model_create")
         self.handle = h
         if fp8 and tuple(kv_scales) != (1.0, 1.0):
@@ -80,6 +88,11 @@ class Model:
             self.set_sampling(generation_config, sampling_seed)
         if logprobs:
             self.set_logprobs(True)
+
+    def weight_bytes(self) -> int:
+        """Resident bytes of the linear-layer weights (ffmi_model_weight_bytes):
+        packed fp16, or bytes plus scales under weight_dtype="fp8"."""
+        return int(F.lib().ffmi_model_weight_bytes(self.handle))
 
     def set_sampling(self, generation_config: Optional[GenerationConfig], seed: int = 0):
         """do_sample: every token of this incremental-decoding model is drawn

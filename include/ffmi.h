@@ -246,6 +246,41 @@ ffmi_status ffmi_linear_ws(const void *X, const void *W_packed, void *Y, int T,
                            int out_dim, int in_dim, int epilogue, void *workspace,
                            size_t workspace_bytes, ffmi_stream stream);
 
+/* fp8 (e4m3) weight-only linear layers (kernels/gemm_w8.hip):
+ *   Y[t][n] = s[n] * sum_k X[t][k] * q[n][k],
+ * X / Y row-major fp16, q[n][k] the OCP e4m3fn byte of W[n][k] / s[n] (fp32
+ * division, clamped to +-448, round to nearest even; the NaN byte is never
+ * written), s[n] = absmax of row n / 448 in fp32 (1 for an all-zero row).  The
+ * bytes are widened to f16 exactly and accumulated in fp32; s[n] multiplies
+ * the sum once.  in_dim % 64 == 0 (else FFMI_ERR_UNSUPPORTED).
+ *   packed bytes: 16 x 64 double blocks of 1 KiB, K-major; out_dim padded to
+ *   16 with zero bytes.  scales: ffmi_linear_w8_scale_count(out_dim) floats
+ *   (out_dim padded to 16).  The _gate_up form interleaves gate and up tiles
+ *   (2i, 2i+1) for FFMI_EPI_SILU_MUL: 2 * packed_bytes, and 2 * scale_count
+ *   scales in the same tile order (16 gate scales, 16 up scales, ...).
+ *   ffmi_linear_w8: epilogue FFMI_EPI_NONE or FFMI_EPI_SILU_MUL, optionally |
+ *   FFMI_W_STREAM; FFMI_X_PACKED / FFMI_Y_PACKED: FFMI_ERR_UNSUPPORTED.  Built
+ *   for T <= 64 (one weight pass); more rows run one pass per 64 rows, each
+ *   re-reading the weights.  A row's result does not depend on T or on the
+ *   rows around it.  workspace: ffmi_linear_w8_workspace_bytes (0 for shapes
+ *   that do not split K); too small, a NULL pointer, T < 0: FFMI_ERR_INVALID.
+ * Every refusal leaves a message naming "w8" in ffmi_last_error. */
+size_t ffmi_linear_w8_packed_bytes(int out_dim, int in_dim);
+size_t ffmi_linear_w8_scale_count(int out_dim);
+ffmi_status ffmi_linear_w8_quantize_pack(const void *W_f16, int out_dim, int in_dim,
+                                         void *W8_packed, float *scales, ffmi_stream stream);
+ffmi_status ffmi_linear_w8_quantize_pack_gate_up(const void *Wg_f16, const void *Wu_f16,
+                                                 int out_dim, int in_dim, void *W8_packed,
+                                                 float *scales, ffmi_stream stream);
+size_t ffmi_linear_w8_workspace_bytes(int T, int out_dim, int in_dim, int epilogue);
+ffmi_status ffmi_linear_w8(const void *X, const void *W8_packed, const float *scales, void *Y,
+                           int T, int out_dim, int in_dim, int epilogue, void *workspace,
+                           size_t workspace_bytes, ffmi_stream stream);
+/* Test hook: row-major [out_dim][in_dim] bytes of a packed buffer; gate_up 0:
+ * a plain buffer, 1 / 2: the gate / up matrix of a _gate_up buffer. */
+ffmi_status ffmi_debug_linear_w8_unpack(const void *W8_packed, int out_dim, int in_dim,
+                                        int gate_up, void *bytes_out, ffmi_stream stream);
+
 /* ------------------------------------------------------------------------ */
 /* Norms (replace Kernels::RMSNorm / ResidualRMSNorm inference_kernel_wrapper, */
 /* rms_norm_kernels.h:50-54, residual_rms_norm_kernels.h:53-59)              */
@@ -597,6 +632,23 @@ ffmi_status ffmi_model_create_ex(const ffmi_llama_config *cfg, const ffmi_model_
  *   was before this flag came and as callers written against that may rely on) */
 #define FFMI_MODEL_KV_FP8 16u
 ffmi_status ffmi_model_set_kv_scales(ffmi_model *m, float k_scale, float v_scale);
+/*   FFMI_MODEL_W8: the linear layers -- fused q/k/v, o, gate/up, down and
+ *   lm_head -- keep fp8 (e4m3) bytes with one fp32 scale per output channel
+ *   (ffmi_linear_w8_quantize_pack, applied to every weight right after its
+ *   fp16 form is made: synthetic, token_chain or checkpoint); only bytes and
+ *   scales stay resident, about half the fp16 model's ffmi_model_weight_bytes.
+ *   The embedding table and the norm weights stay fp16.  Every norm of a step
+ *   is a launch and every GEMM ffmi_linear_w8 writing fp16 rows: no fused
+ *   residual norms, no deferred split-K slabs, no o projection folded into
+ *   the attention, no packed activations.  All three modes, with
+ *   FFMI_MODEL_NATIVE_GQA and FFMI_MODEL_KV_FP8, eager and under graph replay.
+ *   FFMI_ERR_UNSUPPORTED ("w8" in ffmi_last_error): full_precision, tp_size >
+ *   1, FFMI_MODEL_LORA, hidden or intermediate not a multiple of 64.
+ *   (bit value 32; 2 and 8 stay unknown flags) */
+#define FFMI_MODEL_W8 32u
+/* resident bytes of the linear-layer weights (this rank's; packed fp16, or
+ * bytes plus scales under FFMI_MODEL_W8); 0 for a model that does not report */
+size_t ffmi_model_weight_bytes(ffmi_model *m);
 /* LoRA adapters of a FFMI_MODEL_LORA model.  Adapter ids are process-wide
  * (0 .. FFMI_LORA_MAX_ADAPTERS - 1): a request names one at registration
  * (ffmi_rm_register_request_ex) and the model that loaded it serves it.
@@ -1059,7 +1111,10 @@ const char *ffmi_last_error(void);
  * attention projections: ffmi_model_lora_load_modules, _load_folder_ex,
  * ffmi_lora_apply_qkv, ffmi_lora_qkv_workspace_bytes; and the 8-bit KV cache:
  * ffmi_attn_create_ex (FFMI_ATTN_KV_FP8), FFMI_MODEL_KV_FP8,
- * ffmi_model_set_kv_scales */
+ * ffmi_model_set_kv_scales; and fp8 weight-only linear layers:
+ * ffmi_linear_w8(_packed_bytes, _scale_count, _quantize_pack(_gate_up),
+ * _workspace_bytes), ffmi_debug_linear_w8_unpack, FFMI_MODEL_W8,
+ * ffmi_model_weight_bytes */
 const char *ffmi_version(void);
 
 #ifdef __cplusplus
