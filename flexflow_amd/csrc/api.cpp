@@ -726,6 +726,22 @@ extern "C" size_t ffmi_linear_w8_workspace_bytes(int T, int out_dim, int in_dim,
   return ffmi::gemm_w8_workspace_bytes(T, out_dim, in_dim, epilogue);
 }
 
+extern "C" size_t ffmi_linear_w8_onepass_workspace_bytes(int T, int out_dim, int in_dim,
+                                                         int epilogue) {
+  return ffmi::gemm_w8_onepass_workspace_bytes(T, out_dim, in_dim, epilogue);
+}
+
+extern "C" ffmi_status ffmi_debug_linear_w8_plan(int T, int out_dim, int in_dim, int epilogue,
+                                                 size_t workspace_bytes, int *plan) {
+  FFMI_W8_CHECK(plan && T > 0 && out_dim > 0 && in_dim > 0, FFMI_ERR_INVALID,
+                "null plan, T <= 0 or an empty matrix");
+  FFMI_W8_CHECK(in_dim % 64 == 0, FFMI_ERR_UNSUPPORTED, "in_dim % 64 != 0");
+  const ffmi::W8Launch l = ffmi::plan_w8_launch(T, out_dim, in_dim, epilogue, workspace_bytes);
+  plan[0] = l.path, plan[1] = l.MTW, plan[2] = l.NTW, plan[3] = l.S, plan[4] = l.passes;
+  plan[5] = l.nblk;
+  return FFMI_OK;
+}
+
 extern "C" ffmi_status ffmi_linear_w8(const void *X, const void *W8_packed, const float *scales,
                                       void *Y, int T, int out_dim, int in_dim, int epilogue,
                                       void *workspace, size_t workspace_bytes,

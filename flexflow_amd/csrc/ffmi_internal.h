@@ -359,7 +359,18 @@ struct W8Plan {
 };
 W8Plan plan_w8(int N, int K, int epilogue);
 size_t w8_packed_bytes(int N, int K);
-size_t gemm_w8_workspace_bytes(int T, int N, int K, int epilogue);
+size_t gemm_w8_workspace_bytes(int T, int N, int K, int epilogue);  // the minimum: 64 rows of slabs
+// what lets rows above 64 take the M-split kernel (kernels/gemm_w8_mid.hip):
+// slabs for min(T, 256) rows; 0 for a shape that does not split K
+size_t gemm_w8_onepass_workspace_bytes(int T, int N, int K, int epilogue);
+// The launch plan of (T, N, K, epilogue) with ws_bytes of workspace: path 0 the
+// skinny kernel (MTW: m-tiles of the shared chunk, NTW: tiles per wave), 1 the
+// M-split kernel (m-tiles per wave, tiles per workgroup) -- of the first
+// pass; a last pass of <= 64 rows is always a skinny launch.
+struct W8Launch {
+  int path = 0, MTW = 0, NTW = 0, S = 1, passes = 0, nblk = 0, rows = 0;  // rows: per pass
+};
+W8Launch plan_w8_launch(int T, int N, int K, int epilogue, size_t ws_bytes);
 // rows [0, N) of a row-major fp16 matrix (row stride ld) -> destination tiles
 // tile_step * nt + tile_offset and their scales[16 * tile + row]
 hipError_t launch_w8_quantize_pack(const uint16_t *src, int ld, int N, int K, uint8_t *dst,
@@ -368,7 +379,7 @@ hipError_t launch_w8_quantize_pack(const uint16_t *src, int ld, int N, int K, ui
 hipError_t launch_w8_unpack(const uint8_t *src, int N, int K, uint8_t *dst, int tile_step,
                             int tile_offset, int pitch, hipStream_t s);
 // Y [T][N] fp16 rows = s[n] * (X [T][K] . q^T), epilogue FFMI_EPI_NONE /
-// FFMI_EPI_SILU_MUL (| FFMI_W_STREAM); any T (blocks of 64 rows)
+// FFMI_EPI_SILU_MUL (| FFMI_W_STREAM); any T (plan_w8_launch: passes of 256 or 64 rows)
 hipError_t launch_gemm_w8(const uint16_t *X, const uint8_t *W8, const float *scales, uint16_t *Y,
                           float *ws, size_t ws_bytes, int T, int N, int K, int epilogue,
                           hipStream_t s);

@@ -17,7 +17,9 @@
 // the chip reads one contiguous band at a time.  in_dim % 64 == 0; out_dim is
 // padded to 16 (padding rows: zero bytes, scale 1).
 //
-// The GEMM (T <= 64 rows per launch: the weight-bandwidth-bound regime):
+// The GEMM of this file (T <= 64 rows per launch: the weight-bandwidth-bound
+// regime; gemm_w8_mid.hip holds the M-split kernel for 65 .. 256 rows, with
+// the same numerics per row, and plan_w8_launch below chooses between them):
 //  * a workgroup is 4 waves; wave w owns kW8NT adjacent n-tiles, columns
 //    distinct from the other waves', and all four walk the same k-range in
 //    step.  gridDim.x covers the n-tile groups; gridDim.y = S splits K over
@@ -41,36 +43,13 @@
 //    launch_partials_reduce sums in slab order and rounds once.
 // Per output element the order is: the k-steps of the slice in sequence (two
 // MFMAs each), times s[n], then slices 0..S-1 -- fixed by (N, K, flags).
+#include <stdlib.h>
+
 #include <algorithm>
 
-#include "attention_util.h"
+#include "gemm_w8.h"
 
 namespace ffmi {
-
-constexpr int kW8NT = 2;    // n-tiles per wave (even: a gate tile and its up tile)
-constexpr int kW8Ring = 6;  // double blocks in flight per tile and wave
-constexpr int kW8Rows = 64;  // rows per launch; more rows: one launch per block
-constexpr int kW8MaxS = 8;
-constexpr int kW8MinSteps = 4;  // double steps a k-slice keeps at least
-constexpr int kW8Groups = 256;  // workgroups the plan aims for (one per CU)
-
-typedef uint32_t u4v __attribute__((ext_vector_type(4)));
-typedef _Float16 h2w __attribute__((ext_vector_type(2)));
-
-template <bool NTL>
-__device__ __forceinline__ u4v ld_w8(const uint8_t *p) {
-  if constexpr (NTL) return __builtin_nontemporal_load(reinterpret_cast<const u4v *>(p));
-  else return *reinterpret_cast<const u4v *>(p);
-}
-
-// eight e4m3 bytes (a: elements 0-3, b: 4-7) -> an MFMA f16 fragment, exactly
-__device__ __forceinline__ h8 w8_widen(uint32_t a, uint32_t b) {
-  const h2w p0 = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8((int)a, 1.0f, false);
-  const h2w p1 = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8((int)a, 1.0f, true);
-  const h2w p2 = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8((int)b, 1.0f, false);
-  const h2w p3 = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8((int)b, 1.0f, true);
-  return h8{p0[0], p0[1], p1[0], p1[1], p2[0], p2[1], p3[0], p3[1]};
-}
 
 // T <= MT*16 <= 64 rows; X row-major [T][K], K = 64 KT2; W8 / scales as above
 // (pitch = tiles per k-row of the allocation); EPI 1: tiles (2p, 2p+1) =
@@ -349,7 +328,40 @@ static void launch_w8_rows(const W8Plan &p, bool silu, bool ntl, const uint16_t 
 #undef FFMI_W8
 }
 
-// T > kW8Rows: one launch per block of kW8Rows rows (each re-reads the weights)
+size_t gemm_w8_onepass_workspace_bytes(int T, int N, int K, int epilogue) {
+  if (T <= 0 || N <= 0 || K <= 0 || K % 64) return 0;
+  const W8Plan p = plan_w8(N, K, epilogue);
+  return p.S > 1 ? (size_t)p.S * std::min(T, kW8MidRows) * p.ntiles * 16 * sizeof(float) : 0;
+}
+
+// FFMI_W8_MULTIPASS=1: rows above 64 keep one skinny pass per 64 rows, whatever
+// the workspace (A/B against the M-split kernel in one build); once
+static bool sw_w8_multipass() {
+  static const bool v = [] { const char *e = getenv("FFMI_W8_MULTIPASS"); return e && atoi(e) != 0; }();
+  return v;
+}
+
+// The launch plan: what launch_gemm_w8 does and ffmi_debug_linear_w8_plan
+// reports.  Above 64 rows the M-split kernel (gemm_w8_mid.hip) covers 256 rows
+// per weight pass where the workspace holds its slabs (a shape that does not
+// split K needs none); a split shape given only the minimum, the skinny
+// kernel's 64 rows of slabs, keeps one skinny pass per 64 rows -- as plan_gemm
+// un-splits a plan whose workspace is missing.  The bits are the same.
+W8Launch plan_w8_launch(int T, int N, int K, int epilogue, size_t ws_bytes) {
+  W8Launch l;
+  const W8Plan p = plan_w8(N, K, epilogue);
+  l.path = T > kW8Rows && !sw_w8_multipass() &&
+           ws_bytes >= gemm_w8_onepass_workspace_bytes(T, N, K, epilogue);
+  l.rows = l.path ? kW8MidRows : kW8Rows;
+  const int mt = (std::min(T, l.rows) + 15) / 16;  // m-tiles of the first pass
+  l.MTW = l.path ? std::max(2, (mt + 3) / 4) : mt;
+  l.NTW = l.path ? kW8MidNTW : kW8NT;
+  l.S = p.S, l.passes = (T + l.rows - 1) / l.rows, l.nblk = p.nblk;
+  return l;
+}
+
+// One launch per l.rows rows: the M-split kernel for a pass of more than 64
+// rows, the skinny kernel for a shorter (last) one
 hipError_t launch_gemm_w8(const uint16_t *X, const uint8_t *W8, const float *scales, uint16_t *Y,
                           float *ws, size_t ws_bytes, int T, int N, int K, int epilogue,
                           hipStream_t s) {
@@ -361,16 +373,22 @@ hipError_t launch_gemm_w8(const uint16_t *X, const uint8_t *W8, const float *sca
   const W8Plan p = plan_w8(N, K, epilogue);
   if (p.S > 1 && (!ws || ws_bytes < gemm_w8_workspace_bytes(T, N, K, epilogue)))
     return hipErrorInvalidValue;
+  const W8Launch l = plan_w8_launch(T, N, K, epilogue, ws ? ws_bytes : 0);
   const bool silu = base == FFMI_EPI_SILU_MUL, ntl = (epilogue & FFMI_W_STREAM) != 0;
-  for (int t0 = 0; t0 < T; t0 += kW8Rows) {
-    const int Tp = std::min(kW8Rows, T - t0);
+  for (int t0 = 0; t0 < T; t0 += l.rows) {
+    const int Tp = std::min(l.rows, T - t0), mt = (Tp + 15) / 16;
     const uint16_t *Xp = X + (size_t)t0 * K;
     uint16_t *Yp = Y + (size_t)t0 * N;
-    switch ((Tp + 15) / 16) {
-      case 1: launch_w8_rows<1>(p, silu, ntl, Xp, W8, scales, Yp, ws, Tp, N, K, s); break;
-      case 2: launch_w8_rows<2>(p, silu, ntl, Xp, W8, scales, Yp, ws, Tp, N, K, s); break;
-      case 3: launch_w8_rows<3>(p, silu, ntl, Xp, W8, scales, Yp, ws, Tp, N, K, s); break;
-      default: launch_w8_rows<4>(p, silu, ntl, Xp, W8, scales, Yp, ws, Tp, N, K, s); break;
+    if (Tp > kW8Rows) {
+      launch_w8_mid_rows(p, std::max(2, (mt + 3) / 4), silu, ntl, Xp, W8, scales, Yp, ws, Tp, N, K,
+                         s);
+    } else {
+      switch (mt) {
+        case 1: launch_w8_rows<1>(p, silu, ntl, Xp, W8, scales, Yp, ws, Tp, N, K, s); break;
+        case 2: launch_w8_rows<2>(p, silu, ntl, Xp, W8, scales, Yp, ws, Tp, N, K, s); break;
+        case 3: launch_w8_rows<3>(p, silu, ntl, Xp, W8, scales, Yp, ws, Tp, N, K, s); break;
+        default: launch_w8_rows<4>(p, silu, ntl, Xp, W8, scales, Yp, ws, Tp, N, K, s); break;
+      }
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;

@@ -959,12 +959,14 @@ struct LlamaGPU : public ffmi_model {
     {
       // the split-K factor depends on the row-block count, so take the max
       // over every batch size the model can see
-      // (w8: the plan does not depend on T; a launch covers at most 64 rows)
+      // (w8: S does not depend on T; the one-pass size holds the slabs of a
+      // whole M-split launch, up to 256 rows, so a step above 64 rows reads
+      // its weights once per 256 rows)
       if (w8)
-        ws_bytes = std::max({ffmi::gemm_w8_workspace_bytes(Tm, Nqkv, H, 0),
-                             ffmi::gemm_w8_workspace_bytes(Tm, H, Hl, 0),
-                             ffmi::gemm_w8_workspace_bytes(Tm, H, Fl, 0),
-                             ffmi::gemm_w8_workspace_bytes(Tm, Vl, H, 0)});
+        ws_bytes = std::max({ffmi::gemm_w8_onepass_workspace_bytes(Tm, Nqkv, H, 0),
+                             ffmi::gemm_w8_onepass_workspace_bytes(Tm, H, Hl, 0),
+                             ffmi::gemm_w8_onepass_workspace_bytes(Tm, H, Fl, 0),
+                             ffmi::gemm_w8_onepass_workspace_bytes(Tm, Vl, H, 0)});
       for (int t = 16; t <= Tm && !w8; t += 16) {
         const size_t w1 = ffmi_linear_workspace_bytes(t, Nqkv, H, FFMI_EPI_NONE);
         const size_t w2 = ffmi_linear_workspace_bytes(t, H, Hl, FFMI_EPI_NONE);

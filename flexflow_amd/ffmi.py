@@ -185,6 +185,9 @@ SIGNATURES = {
     "ffmi_linear_w8_quantize_pack_gate_up": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p,
                                                      c_void_p, c_void_p]),
     "ffmi_linear_w8_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "ffmi_linear_w8_onepass_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "ffmi_debug_linear_w8_plan": (c_int, [c_int, c_int, c_int, c_int, c_size_t,
+                                          ctypes.POINTER(c_int)]),
     "ffmi_linear_w8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                c_void_p, c_size_t, c_void_p]),
     "ffmi_debug_linear_w8_unpack": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),

@@ -259,11 +259,16 @@ ffmi_status ffmi_linear_ws(const void *X, const void *W_packed, void *Y, int T,
  *   (2i, 2i+1) for FFMI_EPI_SILU_MUL: 2 * packed_bytes, and 2 * scale_count
  *   scales in the same tile order (16 gate scales, 16 up scales, ...).
  *   ffmi_linear_w8: epilogue FFMI_EPI_NONE or FFMI_EPI_SILU_MUL, optionally |
- *   FFMI_W_STREAM; FFMI_X_PACKED / FFMI_Y_PACKED: FFMI_ERR_UNSUPPORTED.  Built
- *   for T <= 64 (one weight pass); more rows run one pass per 64 rows, each
- *   re-reading the weights.  A row's result does not depend on T or on the
- *   rows around it.  workspace: ffmi_linear_w8_workspace_bytes (0 for shapes
- *   that do not split K); too small, a NULL pointer, T < 0: FFMI_ERR_INVALID.
+ *   FFMI_W_STREAM; FFMI_X_PACKED / FFMI_Y_PACKED: FFMI_ERR_UNSUPPORTED.  Two
+ *   kernels, both bound by the weight bytes: T <= 64 rows, and an M-split one
+ *   for 65 .. 256 rows; more rows run one weight pass per 256 rows.  A row's
+ *   result does not depend on T, on the rows around it or on the kernel.
+ *   workspace: at least ffmi_linear_w8_workspace_bytes (0 for shapes that do
+ *   not split K); too small, a NULL pointer, T < 0: FFMI_ERR_INVALID.  That
+ *   minimum holds 64 rows of split-K slabs: with less than
+ *   ffmi_linear_w8_onepass_workspace_bytes (slabs for min(T, 256) rows; 0 for
+ *   shapes that do not split K) a shape that splits K serves T > 64 as one
+ *   pass per 64 rows, each re-reading the weights -- the same bits, slower.
  * Every refusal leaves a message naming "w8" in ffmi_last_error. */
 size_t ffmi_linear_w8_packed_bytes(int out_dim, int in_dim);
 size_t ffmi_linear_w8_scale_count(int out_dim);
@@ -273,9 +278,18 @@ ffmi_status ffmi_linear_w8_quantize_pack_gate_up(const void *Wg_f16, const void 
                                                  int out_dim, int in_dim, void *W8_packed,
                                                  float *scales, ffmi_stream stream);
 size_t ffmi_linear_w8_workspace_bytes(int T, int out_dim, int in_dim, int epilogue);
+size_t ffmi_linear_w8_onepass_workspace_bytes(int T, int out_dim, int in_dim, int epilogue);
 ffmi_status ffmi_linear_w8(const void *X, const void *W8_packed, const float *scales, void *Y,
                            int T, int out_dim, int in_dim, int epilogue, void *workspace,
                            size_t workspace_bytes, ffmi_stream stream);
+/* Test hook (host only, no launch): what ffmi_linear_w8 does with these
+ * arguments and workspace_bytes of workspace, from the plan the launch itself
+ * follows: {path (0 the T <= 64 kernel, 1 M-split), m-tiles (path 0: of the
+ * launch, path 1: per wave), weight tiles (path 0: per wave, path 1: per
+ * workgroup), k-slices S, weight passes, column groups}.  NULL plan, T <= 0:
+ * FFMI_ERR_INVALID; in_dim % 64: FFMI_ERR_UNSUPPORTED. */
+ffmi_status ffmi_debug_linear_w8_plan(int T, int out_dim, int in_dim, int epilogue,
+                                      size_t workspace_bytes, int *plan /* [6] */);
 /* Test hook: row-major [out_dim][in_dim] bytes of a packed buffer; gate_up 0:
  * a plain buffer, 1 / 2: the gate / up matrix of a _gate_up buffer. */
 ffmi_status ffmi_debug_linear_w8_unpack(const void *W8_packed, int out_dim, int in_dim,
@@ -1114,7 +1128,8 @@ const char *ffmi_last_error(void);
  * ffmi_model_set_kv_scales; and fp8 weight-only linear layers:
  * ffmi_linear_w8(_packed_bytes, _scale_count, _quantize_pack(_gate_up),
  * _workspace_bytes), ffmi_debug_linear_w8_unpack, FFMI_MODEL_W8,
- * ffmi_model_weight_bytes */
+ * ffmi_model_weight_bytes; and its M-split kernel for 65 .. 256 rows:
+ * ffmi_linear_w8_onepass_workspace_bytes, ffmi_debug_linear_w8_plan */
 const char *ffmi_version(void);
 
 #ifdef __cplusplus

@@ -17,11 +17,23 @@ weight_dtype "fp16" and "fp8", alternating, after a warm-up generate each.
 --layers n shortens the model (rehearsals); --serve 0 skips this part.
 
     python scripts/linear_w8_bench.py [--out profiles/linear_w8_bench.json]
+
+--mid: the M-split fp8 kernel (65 .. 256 rows in one weight pass) instead.  The
+same five shapes at T = 72, 128, 168, 256, same method, three legs: "onepass"
+(ffmi_linear_w8 with ffmi_linear_w8_onepass_workspace_bytes), "multipass" (the
+same call under FFMI_W8_MULTIPASS=1: one skinny pass per 64 rows) and "fp16".
+The switch is read once per process, so the legs run in two worker processes
+(one with the switch set) that hold their own weight copies and time blocks of
+calls when the parent tells them to, in turn within each round.  No serving
+part: SpecInfer would need a third and fourth model-holding process.
+
+    python scripts/linear_w8_bench.py --mid [--out profiles/linear_w8_mid_bench.json]
 """
 import argparse
 import ctypes
 import json
 import os
+import subprocess
 import sys
 import time
 
@@ -108,6 +120,106 @@ def gemm_rows(args):
     return rows
 
 
+def mid_worker():
+    """stdin: one JSON command per line -- {"shape": i} (weight copies of SHAPES[i]),
+    {"T": t} (activations, output, workspace), {"leg": l, "n": n} (n calls); stdout:
+    one JSON reply per command, a timed block's milliseconds for the last."""
+    fa.set_device(0)
+    L, rng, tm = F.lib(), np.random.default_rng(0), Timer()
+    block16 = f16(rng.standard_normal(8 << 20) * 0.02)
+    block8 = rng.integers(0, 127, size=16 << 20).astype(np.uint8) | \
+        (rng.integers(0, 2, size=16 << 20).astype(np.uint8) << 7)  # (no NaN byte)
+    fp16 = os.environ.get("FFMI_W8_MULTIPASS", "0") == "0"  # (the other worker has no fp16 leg)
+    st, it = {}, 0
+    for line in sys.stdin:
+        cmd, out = json.loads(line), {}
+        if "shape" in cmd:
+            st.clear()  # (frees the last shape's copies first)
+            name, N, K, epi = SHAPES[cmd["shape"]]
+            g = 2 if epi == F.EPI_SILU_MUL else 1
+            b16, b8 = g * L.ffmi_linear_packed_bytes(N, K), g * L.ffmi_linear_w8_packed_bytes(N, K)
+            st.update(N=N, K=K, epi=epi, b16=b16, b8=b8, w8=copies(b8, block8),
+                      w16=copies(b16, block16) if fp16 else None,
+                      sc=Buf(np.full(g * L.ffmi_linear_w8_scale_count(N), 2.0**-6, np.float32)))
+            out = dict(weight_bytes=dict(fp8=int(b8), fp16=int(b16)))
+        elif "T" in cmd:
+            T, N, K, epi = cmd["T"], st["N"], st["K"], st["epi"]
+            X = Buf(f16(rng.standard_normal((T, K))))
+            Xp = Buf.empty((L.ffmi_packed_activation_bytes(T, K),), np.uint8)
+            F.check(L.ffmi_pack_activations(X.ptr, T, K, Xp.ptr, None))
+            nws = max(L.ffmi_linear_workspace_bytes(T, N, K, epi),
+                      L.ffmi_linear_w8_onepass_workspace_bytes(T, N, K, epi), 16)
+            plan = (ctypes.c_int * 6)()
+            F.check(L.ffmi_debug_linear_w8_plan(T, N, K, epi, nws, plan))
+            st.update(T=T, X=X, Xp=Xp, Y=Buf.empty((T, N), np.float16), nws=nws,
+                      ws=Buf.empty((nws,), np.uint8))
+            out = dict(plan=list(plan))
+        else:
+            T, N, K, epi, ws, nws = (st[k] for k in ("T", "N", "K", "epi", "ws", "nws"))
+            tm.start()
+            for _ in range(cmd["n"]):
+                it += 1
+                if cmd["leg"] == "fp16":
+                    (w, n), b = st["w16"], st["b16"]
+                    F.check(L.ffmi_linear_ws(st["Xp"].ptr, ctypes.c_void_p(w.ptr.value + (it % n) * b),
+                                             st["Y"].ptr, T, N, K, epi | F.X_PACKED | F.W_STREAM,
+                                             ws.ptr, nws, None))
+                else:
+                    (w, n), b = st["w8"], st["b8"]
+                    F.check(L.ffmi_linear_w8(st["X"].ptr, ctypes.c_void_p(w.ptr.value + (it % n) * b),
+                                             st["sc"].ptr, st["Y"].ptr, T, N, K, epi | F.W_STREAM,
+                                             ws.ptr, nws, None))
+            out = dict(ms=tm.stop())
+        print(json.dumps(out), flush=True)
+
+
+def mid_rows(args):
+    def worker(multipass):
+        env = dict(os.environ, FFMI_W8_MULTIPASS="1" if multipass else "0")
+        return subprocess.Popen([sys.executable, os.path.abspath(__file__), "--mid-worker"], env=env,
+                                stdin=subprocess.PIPE, stdout=subprocess.PIPE, text=True)
+
+    def ask(w, **cmd):
+        w.stdin.write(json.dumps(cmd) + "\n")
+        w.stdin.flush()
+        line = w.stdout.readline()
+        if not line:
+            raise RuntimeError(f"worker exited with {w.wait()}")
+        return json.loads(line)
+    one, multi = worker(False), worker(True)
+    legs = {"onepass": one, "multipass": multi, "fp16": one}
+    rows = []
+    try:
+        for i, (name, N, K, _) in enumerate(SHAPES):
+            nb = ask(one, shape=i)["weight_bytes"]
+            ask(multi, shape=i)
+            for T in [int(t) for t in args.T.split(",")]:
+                plans = {"onepass": ask(one, T=T)["plan"], "multipass": ask(multi, T=T)["plan"]}
+                assert plans["onepass"][0] == 1 and plans["multipass"][0] == 0, plans
+                us, block = {leg: [] for leg in legs}, {}
+                for leg, w in legs.items():  # warm-up (code objects), then the block's size
+                    ask(w, leg=leg, n=10)
+                    block[leg] = max(20, int(args.window_ms * 20 / ask(w, leg=leg, n=20)["ms"]))
+                for _ in range(args.rounds):
+                    for leg, w in legs.items():
+                        us[leg].append(ask(w, leg=leg, n=block[leg])["ms"] * 1e3 / block[leg])
+                row = dict(gemm=name, T=T, N=N, K=K, rounds=args.rounds, calls_per_block=block,
+                           plan=plans, weight_bytes=nb)
+                for leg in legs:
+                    a = np.array(us[leg])
+                    row[leg] = dict(us=round(float(np.median(a)), 2),
+                                    spread=round(float((a.max() - a.min()) / np.median(a)), 3))
+                row["multipass_over_onepass"] = round(row["multipass"]["us"] / row["onepass"]["us"], 3)
+                row["fp16_over_onepass"] = round(row["fp16"]["us"] / row["onepass"]["us"], 3)
+                print(json.dumps(row), flush=True)
+                rows.append(row)
+    finally:
+        for w in (one, multi):
+            w.stdin.close()
+            w.wait()
+    return rows
+
+
 def serve(args):
     B, P, D = 8, 128, 128
     cfg = dict(LLAMA_7B)
@@ -141,7 +253,9 @@ def serve(args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--T", default="8,32,168")
+    ap.add_argument("--mid", action="store_true", help="the M-split kernel's three legs")
+    ap.add_argument("--mid-worker", action="store_true", help="(a --mid run's child process)")
+    ap.add_argument("--T", default=None, help="default 8,32,168; --mid: 72,128,168,256")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--window-ms", type=float, default=60.0, help="length of a timed block")
     ap.add_argument("--serve", type=int, default=1)
@@ -149,6 +263,17 @@ def main():
     ap.add_argument("--generates", type=int, default=2)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "linear_w8_bench.json"))
     args = ap.parse_args()
+    if args.mid_worker:
+        return mid_worker()
+    args.T = args.T or ("72,128,168,256" if args.mid else "8,32,168")
+    if args.mid:
+        res = dict(bench="linear_w8_mid_bench", gemms=mid_rows(args))
+        out = args.out.replace("linear_w8_bench.json", "linear_w8_mid_bench.json")
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        with open(out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+        return
     fa.set_device(0)
     res = dict(bench="linear_w8_bench", gemms=gemm_rows(args))
     if args.serve:
