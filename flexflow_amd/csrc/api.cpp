@@ -777,6 +777,60 @@ extern "C" ffmi_status ffmi_debug_linear_w8_unpack(const void *W8_packed, int ou
   return FFMI_OK;
 }
 
+// W8A8: fp8 activations with per-token scales (kernels/gemm_w8a8.hip)
+#define FFMI_A8_CHECK(cond, code, why) \
+  do { if (!(cond)) return w8_refuse((code), "w8a8: " why, __LINE__); } while (0)
+
+extern "C" ffmi_status ffmi_quantize_rows_fp8(const void *X_f16, int T, int in_dim, void *X8,
+                                              float *row_scales, ffmi_stream stream) {
+  FFMI_A8_CHECK(X_f16 && X8 && row_scales, FFMI_ERR_INVALID, "null pointer");
+  FFMI_A8_CHECK(T >= 0 && in_dim > 0, FFMI_ERR_INVALID, "T < 0 or an empty row");
+  FFMI_A8_CHECK(in_dim % 64 == 0 && in_dim <= 32768, FFMI_ERR_UNSUPPORTED,
+                "in_dim % 64 != 0 or in_dim > 32768");
+  FFMI_HIP(ffmi::launch_quantize_rows_fp8((const uint16_t *)X_f16, T, in_dim, (uint8_t *)X8,
+                                          row_scales, (hipStream_t)stream));
+  return FFMI_OK;
+}
+
+extern "C" ffmi_status ffmi_rmsnorm_fp8(const void *x1, const void *x2, const void *w,
+                                        void *residual_out, void *X8, float *row_scales, int T,
+                                        int H, float eps, ffmi_stream stream) {
+  FFMI_A8_CHECK(x1 && w && X8 && row_scales && (!x2 || residual_out), FFMI_ERR_INVALID,
+                "null pointer");
+  FFMI_A8_CHECK(T >= 0 && H > 0, FFMI_ERR_INVALID, "T < 0 or an empty row");
+  FFMI_A8_CHECK(H % 64 == 0 && H <= 32768, FFMI_ERR_UNSUPPORTED, "H % 64 != 0 or H > 32768");
+  FFMI_HIP(ffmi::launch_rmsnorm((const uint16_t *)x1, (const uint16_t *)x2, (const uint16_t *)w,
+                                (uint16_t *)residual_out, (uint16_t *)X8, T, H, eps,
+                                (hipStream_t)stream, false, {}, nullptr, nullptr, 0, nullptr,
+                                row_scales));
+  return FFMI_OK;
+}
+
+extern "C" size_t ffmi_linear_w8a8_workspace_bytes(int T, int out_dim, int in_dim, int epilogue) {
+  return ffmi::gemm_w8a8_workspace_bytes(T, out_dim, in_dim, epilogue);
+}
+
+extern "C" ffmi_status ffmi_linear_w8a8(const void *X8, const float *row_scales,
+                                        const void *W8_packed, const float *scales, void *Y, int T,
+                                        int out_dim, int in_dim, int epilogue, void *workspace,
+                                        size_t workspace_bytes, ffmi_stream stream) {
+  FFMI_A8_CHECK(X8 && row_scales && W8_packed && scales && Y, FFMI_ERR_INVALID, "null pointer");
+  FFMI_A8_CHECK(T >= 0 && out_dim > 0 && in_dim > 0, FFMI_ERR_INVALID, "T < 0 or an empty matrix");
+  FFMI_A8_CHECK(in_dim % 64 == 0, FFMI_ERR_UNSUPPORTED, "in_dim % 64 != 0");
+  FFMI_A8_CHECK(!(epilogue & (FFMI_X_PACKED | FFMI_Y_PACKED)), FFMI_ERR_UNSUPPORTED,
+                "row-major activations only (FFMI_X_PACKED / FFMI_Y_PACKED)");
+  const int base = epilogue & ~FFMI_W_STREAM;
+  FFMI_A8_CHECK(base == FFMI_EPI_NONE || base == FFMI_EPI_SILU_MUL, FFMI_ERR_INVALID,
+                "unknown epilogue");
+  const size_t need = ffmi::gemm_w8a8_workspace_bytes(T, out_dim, in_dim, epilogue);
+  FFMI_A8_CHECK(workspace_bytes >= need && (workspace || !need), FFMI_ERR_INVALID,
+                "workspace smaller than ffmi_linear_w8a8_workspace_bytes");
+  FFMI_HIP(ffmi::launch_gemm_w8a8((const uint8_t *)X8, row_scales, (const uint8_t *)W8_packed,
+                                  scales, (uint16_t *)Y, (float *)workspace, workspace_bytes, T,
+                                  out_dim, in_dim, epilogue, (hipStream_t)stream));
+  return FFMI_OK;
+}
+
 extern "C" ffmi_status ffmi_rmsnorm(const void *x, const void *w, void *out, int T, int H,
                                     float eps, ffmi_stream stream) {
   FFMI_CHECK(x && w && out && H % 8 == 0 && H <= 16384, FFMI_ERR_INVALID);

@@ -241,7 +241,7 @@ hipError_t launch_rmsnorm(const uint16_t *x1, const uint16_t *x2, const uint16_t
                           uint16_t *res_out, uint16_t *out, int T, int H, float eps,
                           hipStream_t s, bool out_packed = false, Partials x2p = {}, const char *gather = nullptr,
                           char *blob_dst = nullptr, size_t blob_bytes = 0,
-                          const int32_t *gather_prev = nullptr);
+                          const int32_t *gather_prev = nullptr, float *row_scales = nullptr);
 // FFMI_FAULT_RESID_ROUND negative control (tests only; process-wide)
 void set_norm_fault(bool on);
 hipError_t launch_embedding(const char *blob, int T, const uint16_t *table,
@@ -383,6 +383,19 @@ hipError_t launch_w8_unpack(const uint8_t *src, int N, int K, uint8_t *dst, int 
 hipError_t launch_gemm_w8(const uint16_t *X, const uint8_t *W8, const float *scales, uint16_t *Y,
                           float *ws, size_t ws_bytes, int T, int N, int K, int epilogue,
                           hipStream_t s);
+
+// kernels/gemm_w8a8.hip: W8A8 -- the weights above against e4m3 activation
+// rows with one fp32 scale per row.  X8 [T][K] bytes, within every 64-column
+// block the 8-column chunks in the order 0 4 1 5 2 6 3 7 (the weight layout's);
+// written by launch_quantize_rows_fp8 or by launch_rmsnorm with row_scales.
+hipError_t launch_quantize_rows_fp8(const uint16_t *X, int T, int K, uint8_t *X8, float *row_scales,
+                                    hipStream_t s);
+size_t gemm_w8a8_workspace_bytes(int T, int N, int K, int epilogue);  // slabs for min(T, 256) rows
+// Y [T][N] fp16 rows = a[t] * s[n] * (x8 . q^T); epilogues as launch_gemm_w8's;
+// any T: one weight pass per 256 rows
+hipError_t launch_gemm_w8a8(const uint8_t *X8, const float *row_scales, const uint8_t *W8,
+                            const float *scales, uint16_t *Y, float *ws, size_t ws_bytes, int T,
+                            int N, int K, int epilogue, hipStream_t s);
 
 uint64_t weight_key(const char *name, uint64_t seed);
 

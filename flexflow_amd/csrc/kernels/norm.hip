@@ -8,6 +8,7 @@
 #include <algorithm>
 
 #include "../ffmi_internal.h"
+#include "gemm_w8.h"
 #include "half_bits.h"
 
 namespace ffmi {
@@ -39,14 +40,21 @@ __device__ __forceinline__ T block_sum(T v, T *scratch) {
 //   4 / 5: 1 / 2 with the FFMI_FAULT_RESID_ROUND negative control (tests
 //   only): the sum of squares takes the UNROUNDED fp32 residual sum, where
 //   residual_rms_norm_kernels.cu:112-114 squares the half-rounded one
-template <int NT, int MAXC, int MAXS, int SRC>
+// OUT8 (compile time): the W8A8 input form.  Instead of the fp16 row, `out`
+// takes the row's e4m3 bytes in X8's block order and row_scales[row] its scale
+// (gemm_w8.h), computed from the fp16-rounded out = half(y * w) the plain form
+// would have stored: the bytes of norm + quantize_rows_kernel, bit for bit.
+// res_out is written as in the plain form.
+template <int NT, int MAXC, int MAXS, int SRC, bool OUT8 = false>
 __global__ __launch_bounds__(NT) void rmsnorm_kernel(
     const uint16_t *__restrict__ x1, const uint16_t *__restrict__ x2,
     const uint16_t *__restrict__ w, uint16_t *__restrict__ res_out,
     uint16_t *__restrict__ out, int H, float eps, int out_packed,
     const float *__restrict__ x2p, int pS, int pNP, const char *__restrict__ gather,
-    uint4 *__restrict__ blob_dst, int blob_n16, const int32_t *__restrict__ gprev) {
+    uint4 *__restrict__ blob_dst, int blob_n16, const int32_t *__restrict__ gprev,
+    float *__restrict__ row_scales) {
   __shared__ double scratch[NT / 64];
+  __shared__ uint32_t amax_scratch[OUT8 ? NT / 64 : 1];
   const int row = blockIdx.x;
   const int T = gridDim.x;
   const int nchunk = H >> 3;
@@ -155,6 +163,7 @@ __global__ __launch_bounds__(NT) void rmsnorm_kernel(
   // v_sqrt_f32, ~1 ulp, unless OCML_BASIC_ROUNDED_OPERATIONS is defined)
   const float rms_f = __fdiv_rn(1.0f, sqrtf(__fadd_rn(__fdiv_rn(sum, (float)H), eps)));
   const float rms = h2f_(f2h_(rms_f));
+  uint32_t amax = 0;
 #pragma unroll
   for (int c = 0; c < MAXC; ++c) {
     const int ch = threadIdx.x + c * NT;
@@ -167,8 +176,22 @@ __global__ __launch_bounds__(NT) void rmsnorm_kernel(
         float y = h2f_(f2h_(__fmul_rn(h2f_(e[q]), rms)));
         o8[q] = f2h_(__fmul_rn(y, h2f_(we[q])));
       }
+      if (OUT8) {  // (the row stays in registers until its scale is known)
+        v[c] = *reinterpret_cast<uint4 *>(o8);
+        amax = a8_absmax8(v[c], amax);
+        continue;
+      }
       uint16_t *dst = out_packed ? out + act_packed_off(row, ch * 8, H) : out + (size_t)row * H + ch * 8;
       *reinterpret_cast<uint4 *>(dst) = *reinterpret_cast<uint4 *>(o8);
+    }
+  }
+  if (OUT8) {
+    const float a = a8_row_scale<NT / 64>(amax, amax_scratch);
+    if (threadIdx.x == 0) row_scales[row] = a;
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c) {
+      const int ch = threadIdx.x + c * NT;
+      if (ch < nchunk) a8_store8(reinterpret_cast<uint8_t *>(out), row, H, ch, v[c], a);
     }
   }
 }
@@ -181,7 +204,11 @@ void set_norm_fault(bool on) { g_norm_fault = on; }
 hipError_t launch_rmsnorm(const uint16_t *x1, const uint16_t *x2, const uint16_t *w,
                           uint16_t *res_out, uint16_t *out, int T, int H, float eps,
                           hipStream_t s, bool out_packed, Partials x2p, const char *gather,
-                          char *blob_dst, size_t blob_bytes, const int32_t *gather_prev) {
+                          char *blob_dst, size_t blob_bytes, const int32_t *gather_prev,
+                          float *row_scales) {
+  // row_scales: the W8A8 form -- out takes T * H bytes (X8) and row_scales T
+  // floats; row-major, H % 64, and no split-K slabs (a w8 GEMM reduces its own)
+  if (row_scales && (out_packed || H % 64 || x2p.S > 0)) return hipErrorInvalidValue;
   if (gather && (x2 || x2p.S > 0 || !res_out)) return hipErrorInvalidValue;
   if (blob_dst && (!gather || blob_bytes > (size_t)1 << 30 || (uintptr_t)gather % 16 ||
                    (uintptr_t)blob_dst % 16))
@@ -208,7 +235,7 @@ hipError_t launch_rmsnorm(const uint16_t *x1, const uint16_t *x2, const uint16_t
 #define FFMI_RMS3(NT, MC, MS, SR)                                                              \
   hipLaunchKernelGGL((rmsnorm_kernel<NT, MC, MS, SR>), dim3(T), dim3(NT), 0, s, x1, x2, w,    \
                      res_out, out, H, eps, op, pp, x2p.S, x2p.NP, gather,               \
-                     reinterpret_cast<uint4 *>(blob_dst), blob_n16, gather_prev)
+                     reinterpret_cast<uint4 *>(blob_dst), blob_n16, gather_prev, row_scales)
 #define FFMI_RMS(NT, MC)                                   \
   do {                                                     \
     if (src == 0) FFMI_RMS3(NT, MC, 1, 0);                 \
@@ -225,6 +252,34 @@ hipError_t launch_rmsnorm(const uint16_t *x1, const uint16_t *x2, const uint16_t
     else if (src == 1) FFMI_RMS3(NT, MC, 1, 1);            \
     else FFMI_RMS3(NT, MC, 1, 3);                          \
   } while (0)
+  if (row_scales) {
+#define FFMI_RMS8(NT, MC)                                                                        \
+  hipLaunchKernelGGL((rmsnorm_kernel<NT, MC, 1, SR, true>), dim3(T), dim3(NT), 0, s, x1, x2, w, \
+                     res_out, out, H, eps, 0, pp, 0, 0, gather,                                  \
+                     reinterpret_cast<uint4 *>(blob_dst), blob_n16, gather_prev, row_scales)
+#define FFMI_RMS8_NT                               \
+  do {                                             \
+    if (nchunk <= 128) FFMI_RMS8(128, 1);          \
+    else if (nchunk <= 256) FFMI_RMS8(256, 1);     \
+    else if (nchunk <= 512) FFMI_RMS8(512, 1);     \
+    else if (nchunk <= 1024) FFMI_RMS8(1024, 1);   \
+    else if (nchunk <= 2048) FFMI_RMS8(1024, 2);   \
+    else FFMI_RMS8(1024, 4);                       \
+  } while (0)
+    if (src == 0) {
+      constexpr int SR = 0;
+      FFMI_RMS8_NT;
+    } else if (src == 1) {
+      constexpr int SR = 1;
+      FFMI_RMS8_NT;
+    } else {
+      constexpr int SR = 3;
+      FFMI_RMS8_NT;
+    }
+#undef FFMI_RMS8_NT
+#undef FFMI_RMS8
+    return hipGetLastError();
+  }
   if (g_norm_fault && (src == 1 || src == 2)) {  // negative control (tests only)
 #define FFMI_RMSF(NT)                                      \
   do {                                                     \

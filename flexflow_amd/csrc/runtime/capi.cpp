@@ -22,8 +22,12 @@ extern "C" ffmi_status ffmi_model_create_ex(const ffmi_llama_config *cfg, const 
   if (!flags) return ffmi_model_create(cfg, o, out);
   FFMI_CHECK(cfg && o && out &&
                  (flags & ~(FFMI_MODEL_NATIVE_GQA | FFMI_MODEL_LORA | FFMI_MODEL_KV_FP8 |
-                            FFMI_MODEL_W8)) == 0,
+                            FFMI_MODEL_W8 | FFMI_MODEL_A8)) == 0,
              FFMI_ERR_INVALID);
+  if ((flags & FFMI_MODEL_A8) && !(flags & FFMI_MODEL_W8)) {
+    ffmi_set_last_error("a8: fp8 activations need fp8 weights (FFMI_MODEL_W8)", __FILE__, __LINE__);
+    return FFMI_ERR_UNSUPPORTED;
+  }
   if (flags & FFMI_MODEL_W8) {
     // the fp32 model has no fp8 GEMM; sharded scales and the all-reduce forms,
     // and the LoRA routes on top of the w8 route, are not built

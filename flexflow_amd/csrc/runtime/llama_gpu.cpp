@@ -85,6 +85,13 @@ struct LlamaGPU : public ffmi_model {
   // take: no fused residual norms, no deferred slabs, no folded o projection,
   // row-major activations (packed = false)
   bool w8 = false;
+  // FFMI_MODEL_A8 (with w8): every GEMM input is e4m3 rows with one scale per
+  // token (kernels/gemm_w8a8.hip).  x8 / x8_s hold the input of the GEMM about
+  // to run: written by the quantising norm (qkv, gate/up, lm_head) or by a
+  // quantise launch on att / mlp (o, down), consumed before the next is made
+  bool a8 = false;
+  uint8_t *x8 = nullptr;
+  float *x8_s = nullptr;
   uint8_t *lm8 = nullptr;
   float *lm_s = nullptr;
   size_t wbytes = 0;  // resident bytes of the linear-layer weights
@@ -908,6 +915,10 @@ struct LlamaGPU : public ffmi_model {
     TRY(alloc(&ss_o, (size_t)2 * 32 * (H / 16)));
     ss_d = ss_o + (size_t)32 * (H / 16);
     TRY(alloc(&mlp, (size_t)Tm * Fl));
+    if (a8) {
+      TRY(alloc(&x8, (size_t)Tm * std::max({H, Hl, Fl})));
+      TRY(alloc(&x8_s, (size_t)Tm));
+    }
     if (lora) {
       lora_tab_h.assign((size_t)c.num_layers * kLoraMods * FFMI_LORA_MAX_ADAPTERS, ffmi_lora_entry{});
       TRY(alloc(&lora_tab, lora_tab_h.size()));
@@ -1494,8 +1505,21 @@ struct LlamaGPU : public ffmi_model {
     // the residual norms inside the transport's all-reduces (tp_fuse_norm)
     // (FFMI_MODEL_W8: fuse, fuse_ao, lora and arn are all off, so a step takes
     // the norm launches and the plain GEMM sites below, each of them gemm8)
+    // (FFMI_MODEL_A8: the norms ahead of qkv, gate/up and lm_head write x8 /
+    // x8_s instead of h -- nothing else reads the fp16 normalised rows with
+    // LoRA and TP refused, except the debug taps, whose steps keep the fp16
+    // norm and quantise h, the same bytes; att and mlp are quantised here)
+    const bool norm8 = a8 && !dbg;
+    uint16_t *const hn = norm8 ? reinterpret_cast<uint16_t *>(x8) : h;
+    float *const hs = norm8 ? x8_s : nullptr;
     auto gemm8 = [&](const uint16_t *X, const uint8_t *W, const float *sc, uint16_t *Y, int N, int K,
                      int epi) -> ffmi_status {
+      if (a8) {
+        if (X != h || !norm8) FFMI_HIP(ffmi::launch_quantize_rows_fp8(X, T, K, x8, x8_s, stream));
+        FFMI_HIP(ffmi::launch_gemm_w8a8(x8, x8_s, W, sc, Y, ws, ws_bytes, T, N, K, epi | wstream,
+                                        stream));
+        return FFMI_OK;
+      }
       FFMI_HIP(ffmi::launch_gemm_w8(X, W, sc, Y, ws, ws_bytes, T, N, K, epi | wstream, stream));
       return FFMI_OK;
     };
@@ -1540,11 +1564,11 @@ struct LlamaGPU : public ffmi_model {
         // layer 0: the embedding lookup gathers straight into the first norm
         // (embedding_kernels.cu:233-244; res = the looked-up rows)
         FFMI_HIP(ffmi::launch_rmsnorm(l == 0 ? embed : res, l == 0 ? nullptr : proj, L.in_norm, res,
-                                      h, T, H, eps, stream, packed,
+                                      hn, T, H, eps, stream, packed,
                                       l == 0 ? ffmi::Partials() : down_part,
                                       l == 0 ? (blob_fetch ? batch->host : batch->dev) : nullptr,
                                       l == 0 && blob_fetch ? batch->dev : nullptr, blob_bytes,
-                                      step.slot > 0 ? slot_ids_dev(step.slot - 1) : nullptr));
+                                      step.slot > 0 ? slot_ids_dev(step.slot - 1) : nullptr, hs));
         // the staging is free for the next step once the fetch has read it
         if (l == 0 && blob_fetch && record_upload) FFMI_HIP(hipEventRecord(batch->uploaded, stream));
         prof_end(pr, NORM, (double)T * H * 2 * (l == 0 ? 3 : 4), 0);
@@ -1631,8 +1655,8 @@ struct LlamaGPU : public ffmi_model {
       if (dbg && !arn) TRY(dbg_gemm_out(FFMI_DBG_O_PROJ, l, proj, o_part, T));
       if (!fuse_o && !arn) {
         pr = prof_begin(on);
-        FFMI_HIP(ffmi::launch_rmsnorm(res, proj, L.post_norm, res, h, T, H, eps, stream, packed,
-                                      o_part));
+        FFMI_HIP(ffmi::launch_rmsnorm(res, proj, L.post_norm, res, hn, T, H, eps, stream, packed,
+                                      o_part, nullptr, nullptr, 0, nullptr, hs));
         prof_end(pr, NORM, (double)T * H * 2 * 4, 0);
         mk();
       }
@@ -1704,8 +1728,8 @@ struct LlamaGPU : public ffmi_model {
       if (fuse_d)  // res already holds the last residual add
         FFMI_HIP(ffmi::launch_rmsnorm(res, nullptr, final_norm, nullptr, h, T, H, eps, stream, packed));
       else
-        FFMI_HIP(ffmi::launch_rmsnorm(res, proj, final_norm, res, h, T, H, eps, stream, packed,
-                                      down_part));
+        FFMI_HIP(ffmi::launch_rmsnorm(res, proj, final_norm, res, hn, T, H, eps, stream, packed,
+                                      down_part, nullptr, nullptr, 0, nullptr, hs));
       prof_end(pr, NORM, (double)T * H * 2 * 4, 0);
     }
     mkt();
@@ -1936,6 +1960,7 @@ ffmi_status create_llama_gpu(const ffmi_llama_config *cfg, const ffmi_model_opts
   m->lora = (flags & FFMI_MODEL_LORA) != 0;
   m->kv_fp8 = (flags & FFMI_MODEL_KV_FP8) != 0;
   m->w8 = (flags & FFMI_MODEL_W8) != 0;
+  m->a8 = m->w8 && (flags & FFMI_MODEL_A8) != 0;
   if (m->lora && (o->mode == FFMI_MODEL_BEAM || o->tp_size > 1)) {
     delete m;
     ffmi_set_last_error("lora: INC / TREE models at tp_size 1", __FILE__, __LINE__);

@@ -37,7 +37,8 @@ class Model:
                  weight_init: Union[int, str] = 0, full_precision: bool = False,
                  generation_config: Optional[GenerationConfig] = None, sampling_seed: int = 0,
                  native_gqa: bool = False, logprobs: bool = False, lora: bool = False,
-                 kv_cache_dtype: str = "fp16", kv_scales=(1.0, 1.0), weight_dtype: str = "fp16"):
+                 kv_cache_dtype: str = "fp16", kv_scales=(1.0, 1.0), weight_dtype: str = "fp16",
+                 activation_dtype: str = "fp16"):
         """weights_folder: a checkpoint in the reference's per-tensor format
         (see checkpoint.convert_hf_model); None: seeded synthetic weights,
         `weight_init` "uniform" (0, the bench's), "depth_scaled" (1) or
@@ -57,9 +58,17 @@ class Model:
         keep e4m3 bytes with one fp32 scale per output channel and run the
         fp8-weight GEMM (FFMI_MODEL_W8: about half the weight bytes, see
         weight_bytes; any mode, with native_gqa and kv_cache_dtype="fp8"; not
-        full_precision, tp_size > 1 or lora); "fp16" is the default model."""
+        full_precision, tp_size > 1 or lora); "fp16" is the default model.
+        activation_dtype "fp8" (with weight_dtype "fp8" only): every linear
+        layer's input is e4m3 with one dynamic scale per token and runs on the
+        fp8 matrix instruction (FFMI_MODEL_A8); the residual stream, attention
+        and logits stay fp16."""
         if weight_dtype not in ("fp16", "fp8"):
             raise ValueError(f"weight_dtype {weight_dtype!r}: 'fp16' or 'fp8'")
+        if activation_dtype not in ("fp16", "fp8"):
+            raise ValueError(f"activation_dtype {activation_dtype!r}: 'fp16' or 'fp8'")
+        if activation_dtype == "fp8" and weight_dtype != "fp8":
+            raise ValueError("activation_dtype='fp8' needs weight_dtype='fp8'")
         if kv_cache_dtype not in ("fp16", "fp8"):
             raise ValueError(f"kv_cache_dtype {kv_cache_dtype!r}: 'fp16' or 'fp8'")
         fp8 = kv_cache_dtype == "fp8"
@@ -78,7 +87,9 @@ class Model:
                                        (F.MODEL_NATIVE_GQA if native_gqa else 0) |
                                        (F.MODEL_LORA if lora else 0) |
                                        (F.MODEL_KV_FP8 if fp8 else 0) |
-                                       (F.MODEL_W8 if weight_dtype == "fp8" else 0), ctypes.byref(h)),
+                                       (F.MODEL_W8 if weight_dtype == "fp8" else 0) |
+                                       (F.MODEL_A8 if activation_dtype == "fp8" else 0),
+                                       ctypes.byref(h)),
                 "ffmi_model_create")
         self.handle = h
         if fp8 and tuple(kv_scales) != (1.0, 1.0):

@@ -295,6 +295,42 @@ ffmi_status ffmi_debug_linear_w8_plan(int T, int out_dim, int in_dim, int epilog
 ffmi_status ffmi_debug_linear_w8_unpack(const void *W8_packed, int out_dim, int in_dim,
                                         int gate_up, void *bytes_out, ffmi_stream stream);
 
+/* W8A8 (kernels/gemm_w8a8.hip): the packed fp8 weights above against fp8
+ * (e4m3) activations with one dynamic fp32 scale per token, on the fp8 matrix
+ * instruction (fp32 accumulation; products of two e4m3 values are exact):
+ *   Y[t][n] = a[t] * s[n] * sum_k x8[t][k] * q[n][k]   ((sum * s[n]) * a[t]).
+ *   ffmi_quantize_rows_fp8: a[t] = absmax of row t / 448 (fp32 division; 1 for
+ *   an all-zero row); x8[t][k] the e4m3 byte of X[t][k] / a[t] (fp32 division,
+ *   clamped to +-448, round to nearest even; the NaN byte is never written).
+ *   Inf or NaN in X is outside the contract.  in_dim % 64 == 0, <= 32768.
+ *   The X8 layout is the contract between quantiser and GEMM: [T][in_dim]
+ *   bytes, row-major by row, and within each 64-column block of a row the
+ *   weight layout's order -- for g = 0..3 the 8 bytes of columns 8g .. 8g + 7
+ *   followed by the 8 bytes of columns 32 + 8g .. 32 + 8g + 7.
+ *   ffmi_rmsnorm_fp8: RMSNorm (x2 NULL) or ResidualRMSNorm (x2: residual_out =
+ *   x1 + x2 as ffmi_residual_rmsnorm writes it) whose output row goes out as
+ *   X8 / row_scales instead of fp16 -- quantised from the fp16-rounded values
+ *   the fp16 norm stores, so bit for bit ffmi_(residual_)rmsnorm followed by
+ *   ffmi_quantize_rows_fp8.
+ *   ffmi_linear_w8a8: W8_packed / scales as ffmi_linear_w8's, epilogue
+ *   FFMI_EPI_NONE or FFMI_EPI_SILU_MUL, optionally | FFMI_W_STREAM.  One kernel
+ *   family covers 1 .. 256 rows per weight pass; more rows run one pass per
+ *   256.  A row's result depends on the row, out_dim, in_dim and the epilogue
+ *   only: not on T, the rows around it or the workspace.  workspace: at least
+ *   ffmi_linear_w8a8_workspace_bytes (slabs for min(T, 256) rows; 0 for shapes
+ *   that do not split K) -- there is no multi-pass route with less.
+ * Refusals as ffmi_linear_w8's, naming "w8a8" in ffmi_last_error. */
+ffmi_status ffmi_quantize_rows_fp8(const void *X_f16, int T, int in_dim, void *X8,
+                                   float *row_scales, ffmi_stream stream);
+ffmi_status ffmi_rmsnorm_fp8(const void *x1, const void *x2, const void *w, void *residual_out,
+                             void *X8, float *row_scales, int T, int H, float eps,
+                             ffmi_stream stream);
+size_t ffmi_linear_w8a8_workspace_bytes(int T, int out_dim, int in_dim, int epilogue);
+ffmi_status ffmi_linear_w8a8(const void *X8, const float *row_scales, const void *W8_packed,
+                             const float *scales, void *Y, int T, int out_dim, int in_dim,
+                             int epilogue, void *workspace, size_t workspace_bytes,
+                             ffmi_stream stream);
+
 /* ------------------------------------------------------------------------ */
 /* Norms (replace Kernels::RMSNorm / ResidualRMSNorm inference_kernel_wrapper, */
 /* rms_norm_kernels.h:50-54, residual_rms_norm_kernels.h:53-59)              */
@@ -660,6 +696,16 @@ ffmi_status ffmi_model_set_kv_scales(ffmi_model *m, float k_scale, float v_scale
  *   1, FFMI_MODEL_LORA, hidden or intermediate not a multiple of 64.
  *   (bit value 32; 2 and 8 stay unknown flags) */
 #define FFMI_MODEL_W8 32u
+/*   FFMI_MODEL_A8: on top of FFMI_MODEL_W8, every linear layer's input is fp8
+ *   (e4m3) with one dynamic scale per token and every GEMM ffmi_linear_w8a8.
+ *   The step is the W8 step with every norm that feeds a GEMM the quantising
+ *   norm (ffmi_rmsnorm_fp8) and a ffmi_quantize_rows_fp8 launch before o_proj
+ *   and before down_proj; the residual stream, the attention and the logits
+ *   stay fp16; weights and ffmi_model_weight_bytes are those of W8.  Valid
+ *   only together with FFMI_MODEL_W8 (alone: FFMI_ERR_UNSUPPORTED, "a8" in
+ *   ffmi_last_error); W8's refusals carry over.
+ *   (bit value 128: 64, like 2 and 8, stays an unknown flag, FFMI_ERR_INVALID) */
+#define FFMI_MODEL_A8 128u
 /* resident bytes of the linear-layer weights (this rank's; packed fp16, or
  * bytes plus scales under FFMI_MODEL_W8); 0 for a model that does not report */
 size_t ffmi_model_weight_bytes(ffmi_model *m);
@@ -1129,7 +1175,9 @@ const char *ffmi_last_error(void);
  * ffmi_linear_w8(_packed_bytes, _scale_count, _quantize_pack(_gate_up),
  * _workspace_bytes), ffmi_debug_linear_w8_unpack, FFMI_MODEL_W8,
  * ffmi_model_weight_bytes; and its M-split kernel for 65 .. 256 rows:
- * ffmi_linear_w8_onepass_workspace_bytes, ffmi_debug_linear_w8_plan */
+ * ffmi_linear_w8_onepass_workspace_bytes, ffmi_debug_linear_w8_plan; and fp8
+ * activations with per-token scales (W8A8): ffmi_quantize_rows_fp8,
+ * ffmi_rmsnorm_fp8, ffmi_linear_w8a8(_workspace_bytes), FFMI_MODEL_A8 */
 const char *ffmi_version(void);
 
 #ifdef __cplusplus

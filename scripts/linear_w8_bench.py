@@ -28,6 +28,18 @@ calls when the parent tells them to, in turn within each round.  No serving
 part: SpecInfer would need a third and fourth model-holding process.
 
     python scripts/linear_w8_bench.py --mid [--out profiles/linear_w8_mid_bench.json]
+
+--a8: W8A8 (fp8 activations with per-token scales on the fp8 matrix
+instruction).  The same five shapes, cold-weight protocol and method at T = 8
+and 168, three legs alternating in one process: "a8" (ffmi_linear_w8a8; for
+o_proj and down, whose input no norm produces, the ffmi_quantize_rows_fp8 launch
+ahead of it is inside the timed call), "w8a16" (ffmi_linear_w8 with its one-pass
+workspace: the M-split kernel at T = 168, as --mid's "onepass") and "fp16".
+Then the quantising norm against the plain one (ffmi_rmsnorm_fp8 /
+ffmi_rmsnorm, H = 4096), and the serving part with weight_dtype "fp8" against
+"fp8" + activation_dtype "fp8".
+
+    python scripts/linear_w8_bench.py --a8 [--out profiles/linear_w8a8_bench.json]
 """
 import argparse
 import ctypes
@@ -118,6 +130,97 @@ def gemm_rows(args):
             print(json.dumps(row), flush=True)
             rows.append(row)
     return rows
+
+
+def timed_legs(args, legs):
+    """legs: name -> calls(n); alternating blocks -> name -> {us, spread}, blocks"""
+    us, block, tm = {leg: [] for leg in legs}, {}, Timer()
+    for leg, calls in legs.items():  # warm-up (code objects), then the block's size
+        calls(10)
+        tm.start()
+        calls(20)
+        block[leg] = max(20, int(args.window_ms * 20 / tm.stop()))
+    for _ in range(args.rounds):
+        for leg, calls in legs.items():
+            tm.start()
+            calls(block[leg])
+            us[leg].append(tm.stop() * 1e3 / block[leg])
+    return {leg: dict(us=round(float(np.median(a)), 2),
+                      spread=round(float((max(a) - min(a)) / np.median(a)), 3))
+            for leg, a in us.items()}, block
+
+
+def a8_rows(args):
+    L, rng, rows = F.lib(), np.random.default_rng(0), []
+    block16 = f16(rng.standard_normal(8 << 20) * 0.02)
+    block8 = rng.integers(0, 127, size=16 << 20).astype(np.uint8) | \
+        (rng.integers(0, 2, size=16 << 20).astype(np.uint8) << 7)  # (no NaN byte)
+    Ts = [int(t) for t in args.T.split(",")]
+    for name, N, K, epi in SHAPES:
+        g = 2 if epi == F.EPI_SILU_MUL else 1
+        b16, b8 = g * L.ffmi_linear_packed_bytes(N, K), g * L.ffmi_linear_w8_packed_bytes(N, K)
+        (w16, n16), (w8, n8) = copies(b16, block16), copies(b8, block8)
+        sc = Buf(np.full(g * L.ffmi_linear_w8_scale_count(N), 2.0**-6, np.float32))
+        quant = name in ("o_proj", "down")  # (the other inputs come quantised from a norm)
+        for T in Ts:
+            X = Buf(f16(rng.standard_normal((T, K))))
+            Xp = Buf.empty((L.ffmi_packed_activation_bytes(T, K),), np.uint8)
+            F.check(L.ffmi_pack_activations(X.ptr, T, K, Xp.ptr, None))
+            X8, xs, Y = Buf.empty((T, K), np.uint8), Buf.empty((T,), np.float32), Buf.empty((T, N), np.float16)
+            F.check(L.ffmi_quantize_rows_fp8(X.ptr, T, K, X8.ptr, xs.ptr, None))
+            nws = max(L.ffmi_linear_workspace_bytes(T, N, K, epi), 16,
+                      L.ffmi_linear_w8_onepass_workspace_bytes(T, N, K, epi),
+                      L.ffmi_linear_w8a8_workspace_bytes(T, N, K, epi))
+            ws, it = Buf.empty((nws,), np.uint8), [0]
+
+            def wt(base, n, b):
+                it[0] += 1
+                return ctypes.c_void_p(base.ptr.value + (it[0] % n) * b)
+
+            def a8(n):
+                for _ in range(n):
+                    if quant:
+                        F.check(L.ffmi_quantize_rows_fp8(X.ptr, T, K, X8.ptr, xs.ptr, None))
+                    F.check(L.ffmi_linear_w8a8(X8.ptr, xs.ptr, wt(w8, n8, b8), sc.ptr, Y.ptr, T, N, K,
+                                               epi | F.W_STREAM, ws.ptr, nws, None))
+
+            def w8a16(n):
+                for _ in range(n):
+                    F.check(L.ffmi_linear_w8(X.ptr, wt(w8, n8, b8), sc.ptr, Y.ptr, T, N, K,
+                                             epi | F.W_STREAM, ws.ptr, nws, None))
+
+            def fp16(n):
+                for _ in range(n):
+                    F.check(L.ffmi_linear_ws(Xp.ptr, wt(w16, n16, b16), Y.ptr, T, N, K,
+                                             epi | F.X_PACKED | F.W_STREAM, ws.ptr, nws, None))
+            res, block = timed_legs(args, dict(a8=a8, w8a16=w8a16, fp16=fp16))
+            row = dict(gemm=name, T=T, N=N, K=K, rounds=args.rounds, calls_per_block=block,
+                       a8_includes_quantise=quant, weight_bytes=dict(fp8=int(b8), fp16=int(b16)), **res)
+            row["w8a16_over_a8"] = round(res["w8a16"]["us"] / res["a8"]["us"], 3)
+            row["fp16_over_a8"] = round(res["fp16"]["us"] / res["a8"]["us"], 3)
+            print(json.dumps(row), flush=True)
+            rows.append(row)
+    norms = []
+    for T in Ts:  # the quantising norm against the plain one, residual form
+        x1, x2, w = (Buf(f16(rng.standard_normal(s))) for s in ((T, H), (T, H), (H,)))
+        res_o, out = Buf.empty((T, H), np.float16), Buf.empty((T, H), np.float16)
+        X8, xs = Buf.empty((T, H), np.uint8), Buf.empty((T,), np.float32)
+
+        def plain(n):
+            for _ in range(n):
+                F.check(L.ffmi_residual_rmsnorm(x1.ptr, x2.ptr, w.ptr, res_o.ptr, out.ptr, T, H, 1e-6, None))
+
+        def fused(n):
+            for _ in range(n):
+                F.check(L.ffmi_rmsnorm_fp8(x1.ptr, x2.ptr, w.ptr, res_o.ptr, X8.ptr, xs.ptr, T, H, 1e-6, None))
+
+        def standalone(n):
+            for _ in range(n):
+                F.check(L.ffmi_quantize_rows_fp8(out.ptr, T, H, X8.ptr, xs.ptr, None))
+        res, _ = timed_legs(args, dict(norm_fp16=plain, norm_fp8=fused, quantize_rows=standalone))
+        norms.append(dict(T=T, H=H, **res))
+        print(json.dumps(norms[-1]), flush=True)
+    return rows, norms
 
 
 def mid_worker():
@@ -227,8 +330,10 @@ def serve(args):
         cfg["num_layers"] = args.layers
     rm_kw = dict(max_requests_per_batch=B, max_tokens_per_batch=1024, max_sequence_length=512)
     prompts = make_prompts(B, P - 1, cfg["vocab_size"])
+    kinds = {"fp8": dict(weight_dtype="fp8"), "fp8_a8": dict(weight_dtype="fp8", activation_dtype="fp8")} \
+        if args.a8 else {d: dict(weight_dtype=d) for d in ("fp16", "fp8")}
     models = {d: fa.Model(cfg, "inc", max_requests=B, max_tokens=1024, max_seq_len=512,
-                          weight_seed=20250117, weight_dtype=d) for d in ("fp16", "fp8")}
+                          weight_seed=20250117, **kw) for d, kw in kinds.items()}
 
     def generates(m, n):
         new, t0 = 0, time.time()
@@ -245,7 +350,8 @@ def serve(args):
     med = {d: sorted(v)[len(v) // 2] for d, v in rates.items()}
     out = dict(workload=f"llama7b_incr B={B} P={P} D={D} layers={cfg['num_layers']}",
                generates_per_window=args.generates, tokens_per_s=rates, median=med,
-               fp8_over_fp16=round(med["fp8"] / med["fp16"], 4),
+               **({"fp8_a8_over_fp8": round(med["fp8_a8"] / med["fp8"], 4)} if args.a8 else
+                  {"fp8_over_fp16": round(med["fp8"] / med["fp16"], 4)}),
                weight_bytes={d: m.weight_bytes() for d, m in models.items()})
     print(json.dumps(out), flush=True)
     return out
@@ -254,6 +360,7 @@ def serve(args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mid", action="store_true", help="the M-split kernel's three legs")
+    ap.add_argument("--a8", action="store_true", help="the W8A8 legs")
     ap.add_argument("--mid-worker", action="store_true", help="(a --mid run's child process)")
     ap.add_argument("--T", default=None, help="default 8,32,168; --mid: 72,128,168,256")
     ap.add_argument("--rounds", type=int, default=5)
@@ -265,7 +372,19 @@ def main():
     args = ap.parse_args()
     if args.mid_worker:
         return mid_worker()
-    args.T = args.T or ("72,128,168,256" if args.mid else "8,32,168")
+    args.T = args.T or ("8,168" if args.a8 else "72,128,168,256" if args.mid else "8,32,168")
+    if args.a8:
+        fa.set_device(0)
+        gemms, norms = a8_rows(args)
+        res = dict(bench="linear_w8a8_bench", gemms=gemms, norms=norms)
+        if args.serve:
+            res["serving"] = serve(args)
+        out = args.out.replace("linear_w8_bench.json", "linear_w8a8_bench.json")
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        with open(out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+        return
     if args.mid:
         res = dict(bench="linear_w8_mid_bench", gemms=mid_rows(args))
         out = args.out.replace("linear_w8_bench.json", "linear_w8_mid_bench.json")

@@ -1,0 +1,66 @@
+"""The W8A8 additions to the C ABI (include/ffmi.h) that need no GPU: the
+workspace size, the refusals (naming "a8") and the model flag's rules."""
+import ctypes
+
+import pytest
+
+import flexflow_amd as fa
+import flexflow_amd.ffmi as F
+
+INVALID, UNSUPPORTED = 1, 5
+
+
+def refused(fn, st, *args):
+    assert fn(*args) == st and "a8" in F.lib().ffmi_last_error().decode(), args
+
+
+def test_linear_w8a8_refusals_and_the_one_pass_workspace():
+    L = F.lib()
+    buf = ctypes.create_string_buffer(64)
+    p = ctypes.addressof(buf)  # (never dereferenced: every call below is refused first)
+    for T in (1, 64, 168, 300):  # S = 8 slabs of min(T, 256) rows x 16 padded columns
+        assert L.ffmi_linear_w8a8_workspace_bytes(T, 16, 4096, 0) == 8 * min(T, 256) * 16 * 4
+        assert L.ffmi_linear_w8a8_workspace_bytes(T, 16, 4096, F.EPI_SILU_MUL) == 0
+    gemm = L.ffmi_linear_w8a8
+    for i in range(5):  # X8, row scales, W8, scales, Y
+        ptrs = [None if j == i else p for j in range(5)]
+        refused(gemm, INVALID, *ptrs, 8, 16, 64, 0, None, 0, None)
+    refused(gemm, INVALID, p, p, p, p, p, -1, 16, 64, 0, None, 0, None)
+    refused(gemm, UNSUPPORTED, p, p, p, p, p, 8, 16, 96, 0, None, 0, None)
+    for flag in (F.X_PACKED, F.Y_PACKED):
+        refused(gemm, UNSUPPORTED, p, p, p, p, p, 8, 64, 64, flag, None, 0, None)
+    need = L.ffmi_linear_w8a8_workspace_bytes(8, 16, 4096, 0)
+    assert need > 0
+    refused(gemm, INVALID, p, p, p, p, p, 8, 16, 4096, 0, p, need - 4, None)
+    refused(gemm, INVALID, p, p, p, p, p, 8, 16, 4096, 0, None, need, None)
+    refused(L.ffmi_quantize_rows_fp8, INVALID, None, 8, 64, p, p, None)
+    refused(L.ffmi_quantize_rows_fp8, INVALID, p, 8, 64, p, None, None)
+    refused(L.ffmi_quantize_rows_fp8, UNSUPPORTED, p, 8, 96, p, p, None)
+    refused(L.ffmi_rmsnorm_fp8, INVALID, p, None, p, None, None, p, 8, 64, 1e-6, None)
+    refused(L.ffmi_rmsnorm_fp8, INVALID, p, p, p, None, p, p, 8, 64, 1e-6, None)  # x2 without res
+    refused(L.ffmi_rmsnorm_fp8, UNSUPPORTED, p, None, p, None, p, p, 8, 96, 1e-6, None)
+
+
+def test_model_flag_a8_rules_before_the_device():
+    L = F.lib()
+    c = F.LlamaConfig.from_dict(dict(num_layers=1, vocab_size=1000, num_heads=8, hidden=512,
+                                     intermediate=1024))
+    m = ctypes.c_void_p()
+
+    def opts(tp_size=1, full_precision=0):
+        return F.ModelOpts(F.MODEL_INC, 0, tp_size, None, 2, 16, 64, 0, 1, 0, None, 0, full_precision)
+
+    def create(o, flags):
+        return L.ffmi_model_create_ex(ctypes.byref(c), ctypes.byref(o), flags, ctypes.byref(m))
+    assert F.MODEL_A8 == 128
+    assert create(opts(), F.MODEL_A8) == UNSUPPORTED and "a8" in L.ffmi_last_error().decode()
+    both = F.MODEL_A8 | F.MODEL_W8
+    for o, flags in ((opts(full_precision=1), both), (opts(tp_size=2), both),
+                     (opts(), both | F.MODEL_LORA)):
+        assert create(o, flags) == UNSUPPORTED and "w8" in L.ffmi_last_error().decode()
+    assert create(opts(), both | 64) == INVALID and create(opts(), 64) == INVALID
+    cfg = dict(num_layers=1, vocab_size=100, num_heads=2, hidden=128, intermediate=256)
+    with pytest.raises(ValueError, match="activation_dtype"):
+        fa.Model(cfg, "inc", activation_dtype="fp8")
+    with pytest.raises(ValueError, match="activation_dtype"):
+        fa.Model(cfg, "inc", weight_dtype="fp8", activation_dtype="int8")
