@@ -777,6 +777,90 @@ extern "C" ffmi_status ffmi_debug_linear_w8_unpack(const void *W8_packed, int ou
   return FFMI_OK;
 }
 
+// MXFP4 weight-only linear layers (kernels/gemm_w4.hip)
+#define FFMI_W4_CHECK(cond, code, why) \
+  do { if (!(cond)) return w8_refuse((code), "w4: " why, __LINE__); } while (0)
+
+extern "C" size_t ffmi_linear_w4_packed_bytes(int out_dim, int in_dim) {
+  if (out_dim <= 0 || in_dim <= 0 || in_dim % 128) return 0;
+  return ffmi::w4_packed_bytes(out_dim, in_dim);
+}
+
+extern "C" size_t ffmi_linear_w4_scale_bytes(int out_dim, int in_dim) {
+  if (out_dim <= 0 || in_dim <= 0 || in_dim % 128) return 0;
+  return ffmi::w4_scale_bytes(out_dim, in_dim);
+}
+
+extern "C" ffmi_status ffmi_linear_w4_quantize_pack(const void *W_f16, int out_dim, int in_dim,
+                                                    void *W4_packed, void *scales,
+                                                    ffmi_stream stream) {
+  FFMI_W4_CHECK(W_f16 && W4_packed && scales && out_dim > 0 && in_dim > 0, FFMI_ERR_INVALID,
+                "null pointer or empty matrix");
+  FFMI_W4_CHECK(in_dim % 128 == 0, FFMI_ERR_UNSUPPORTED, "in_dim % 128 != 0");
+  FFMI_HIP(ffmi::launch_w4_quantize_pack((const uint16_t *)W_f16, in_dim, out_dim, in_dim,
+                                         (uint8_t *)W4_packed, (uint8_t *)scales, 1, 0,
+                                         (out_dim + 15) / 16, (hipStream_t)stream));
+  return FFMI_OK;
+}
+
+extern "C" ffmi_status ffmi_linear_w4_quantize_pack_gate_up(const void *Wg_f16, const void *Wu_f16,
+                                                            int out_dim, int in_dim,
+                                                            void *W4_packed, void *scales,
+                                                            ffmi_stream stream) {
+  FFMI_W4_CHECK(Wg_f16 && Wu_f16 && W4_packed && scales && out_dim > 0 && in_dim > 0,
+                FFMI_ERR_INVALID, "null pointer or empty matrix");
+  FFMI_W4_CHECK(in_dim % 128 == 0, FFMI_ERR_UNSUPPORTED, "in_dim % 128 != 0");
+  const int pitch = 2 * ((out_dim + 15) / 16);
+  FFMI_HIP(ffmi::launch_w4_quantize_pack((const uint16_t *)Wg_f16, in_dim, out_dim, in_dim,
+                                         (uint8_t *)W4_packed, (uint8_t *)scales, 2, 0, pitch,
+                                         (hipStream_t)stream));
+  FFMI_HIP(ffmi::launch_w4_quantize_pack((const uint16_t *)Wu_f16, in_dim, out_dim, in_dim,
+                                         (uint8_t *)W4_packed, (uint8_t *)scales, 2, 1, pitch,
+                                         (hipStream_t)stream));
+  return FFMI_OK;
+}
+
+extern "C" size_t ffmi_linear_w4_workspace_bytes(int T, int out_dim, int in_dim, int epilogue) {
+  return ffmi::gemm_w4_workspace_bytes(T, out_dim, in_dim, epilogue);
+}
+
+extern "C" ffmi_status ffmi_linear_w4(const void *X, const void *W4_packed, const void *scales,
+                                      void *Y, int T, int out_dim, int in_dim, int epilogue,
+                                      void *workspace, size_t workspace_bytes,
+                                      ffmi_stream stream) {
+  FFMI_W4_CHECK(X && W4_packed && scales && Y, FFMI_ERR_INVALID, "null pointer");
+  FFMI_W4_CHECK(T >= 0 && out_dim > 0 && in_dim > 0, FFMI_ERR_INVALID, "T < 0 or an empty matrix");
+  FFMI_W4_CHECK(in_dim % 128 == 0, FFMI_ERR_UNSUPPORTED, "in_dim % 128 != 0");
+  FFMI_W4_CHECK(!(epilogue & (FFMI_X_PACKED | FFMI_Y_PACKED)), FFMI_ERR_UNSUPPORTED,
+                "row-major activations only (FFMI_X_PACKED / FFMI_Y_PACKED)");
+  const int base = epilogue & ~FFMI_W_STREAM;
+  FFMI_W4_CHECK(base == FFMI_EPI_NONE || base == FFMI_EPI_SILU_MUL, FFMI_ERR_INVALID,
+                "unknown epilogue");
+  const size_t need = ffmi::gemm_w4_workspace_bytes(T, out_dim, in_dim, epilogue);
+  FFMI_W4_CHECK(workspace_bytes >= need && (workspace || !need), FFMI_ERR_INVALID,
+                "workspace smaller than ffmi_linear_w4_workspace_bytes");
+  FFMI_HIP(ffmi::launch_gemm_w4((const uint16_t *)X, (const uint8_t *)W4_packed,
+                                (const uint8_t *)scales, (uint16_t *)Y, (float *)workspace,
+                                workspace_bytes, T, out_dim, in_dim, epilogue, (hipStream_t)stream));
+  return FFMI_OK;
+}
+
+extern "C" ffmi_status ffmi_debug_linear_w4_unpack(const void *W4_packed, const void *scales,
+                                                   int out_dim, int in_dim, int gate_up,
+                                                   void *nibbles_out, void *scales_out,
+                                                   ffmi_stream stream) {
+  FFMI_W4_CHECK(W4_packed && scales && nibbles_out && scales_out && out_dim > 0 && in_dim > 0,
+                FFMI_ERR_INVALID, "null pointer or empty matrix");
+  FFMI_W4_CHECK(in_dim % 128 == 0, FFMI_ERR_UNSUPPORTED, "in_dim % 128 != 0");
+  FFMI_W4_CHECK(gate_up >= 0 && gate_up <= 2, FFMI_ERR_INVALID, "gate_up: 0, 1 (gate) or 2 (up)");
+  const int nt = (out_dim + 15) / 16;
+  FFMI_HIP(ffmi::launch_w4_unpack((const uint8_t *)W4_packed, (const uint8_t *)scales, out_dim,
+                                  in_dim, (uint8_t *)nibbles_out, (uint8_t *)scales_out,
+                                  gate_up ? 2 : 1, gate_up == 2 ? 1 : 0, gate_up ? 2 * nt : nt,
+                                  (hipStream_t)stream));
+  return FFMI_OK;
+}
+
 // W8A8: fp8 activations with per-token scales (kernels/gemm_w8a8.hip)
 #define FFMI_A8_CHECK(cond, code, why) \
   do { if (!(cond)) return w8_refuse((code), "w8a8: " why, __LINE__); } while (0)

@@ -397,6 +397,30 @@ hipError_t launch_gemm_w8a8(const uint8_t *X8, const float *row_scales, const ui
                             const float *scales, uint16_t *Y, float *ws, size_t ws_bytes, int T,
                             int N, int K, int epilogue, hipStream_t s);
 
+// kernels/gemm_w4.hip: OCP MXFP4 weight-only linear layers.  W4: 1 KiB quad
+// blocks (16 rows x 128 k of e2m1 nibbles), scales: 64 bytes of e8m0 per quad
+// block; both K-major, `pitch` tiles per k-row.  plan_w4 depends on (N, K,
+// epilogue) only.
+struct W4Plan {
+  int ntiles = 0, nblk = 0, KT4 = 0, S = 1;  // 16-column tiles, tile groups, k/128, k-slices
+};
+W4Plan plan_w4(int N, int K, int epilogue);
+size_t w4_packed_bytes(int N, int K);
+size_t w4_scale_bytes(int N, int K);
+size_t gemm_w4_workspace_bytes(int T, int N, int K, int epilogue);  // slabs for min(T, 64) rows
+// rows [0, N) of a row-major fp16 matrix (row stride ld) -> destination tiles
+// tile_step * nt + tile_offset of the nibble and of the scale array
+hipError_t launch_w4_quantize_pack(const uint16_t *src, int ld, int N, int K, uint8_t *dst,
+                                   uint8_t *scales, int tile_step, int tile_offset, int pitch,
+                                   hipStream_t s);
+hipError_t launch_w4_unpack(const uint8_t *src, const uint8_t *scales, int N, int K, uint8_t *nib,
+                            uint8_t *sc, int tile_step, int tile_offset, int pitch, hipStream_t s);
+// Y [T][N] fp16 rows = X [T][K] . deq^T, epilogue FFMI_EPI_NONE /
+// FFMI_EPI_SILU_MUL (| FFMI_W_STREAM); any T: one pass per 64 rows
+hipError_t launch_gemm_w4(const uint16_t *X, const uint8_t *W4, const uint8_t *scales, uint16_t *Y,
+                          float *ws, size_t ws_bytes, int T, int N, int K, int epilogue,
+                          hipStream_t s);
+
 uint64_t weight_key(const char *name, uint64_t seed);
 
 }  // namespace ffmi

@@ -22,8 +22,21 @@ extern "C" ffmi_status ffmi_model_create_ex(const ffmi_llama_config *cfg, const 
   if (!flags) return ffmi_model_create(cfg, o, out);
   FFMI_CHECK(cfg && o && out &&
                  (flags & ~(FFMI_MODEL_NATIVE_GQA | FFMI_MODEL_LORA | FFMI_MODEL_KV_FP8 |
-                            FFMI_MODEL_W8 | FFMI_MODEL_A8)) == 0,
+                            FFMI_MODEL_W8 | FFMI_MODEL_A8 | FFMI_MODEL_W4)) == 0,
              FFMI_ERR_INVALID);
+  if (flags & FFMI_MODEL_W4) {
+    // one weight format per model; otherwise what the w8 route leaves unbuilt
+    const char *why = (flags & (FFMI_MODEL_W8 | FFMI_MODEL_A8))
+                          ? "w4: not together with FFMI_MODEL_W8 / FFMI_MODEL_A8"
+                      : o->full_precision           ? "w4: fp16 models only (full_precision)"
+                      : o->tp_size > 1              ? "w4: tp_size > 1"
+                      : (flags & FFMI_MODEL_LORA)   ? "w4: LoRA adapters on MXFP4 weights are not served"
+                                                    : nullptr;
+    if (why) {
+      ffmi_set_last_error(why, __FILE__, __LINE__);
+      return FFMI_ERR_UNSUPPORTED;
+    }
+  }
   if ((flags & FFMI_MODEL_A8) && !(flags & FFMI_MODEL_W8)) {
     ffmi_set_last_error("a8: fp8 activations need fp8 weights (FFMI_MODEL_W8)", __FILE__, __LINE__);
     return FFMI_ERR_UNSUPPORTED;

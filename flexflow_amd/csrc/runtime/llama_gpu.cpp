@@ -90,6 +90,10 @@ struct LlamaGPU : public ffmi_model {
   // to run: written by the quantising norm (qkv, gate/up, lm_head) or by a
   // quantise launch on att / mlp (o, down), consumed before the next is made
   bool a8 = false;
+  // FFMI_MODEL_W4: the w8 route (wq = w8 || w4 selects it) with OCP MXFP4
+  // weights (kernels/gemm_w4.hip): the byte pointers hold the nibbles, the
+  // scale pointers the e8m0 scale bytes, and every GEMM is launch_gemm_w4
+  bool w4 = false, wq = false;
   uint8_t *x8 = nullptr;
   float *x8_s = nullptr;
   uint8_t *lm8 = nullptr;
@@ -607,7 +611,7 @@ struct LlamaGPU : public ffmi_model {
     return n;
   }
   double gemm_bytes(int T, int N_w, int N_out, int K) const {
-    return (w8 ? 1.0 : 2.0) * N_w * K + 2.0 * ((double)T * K + (double)T * N_out);
+    return (w4 ? 0.53125 : w8 ? 1.0 : 2.0) * N_w * K + 2.0 * ((double)T * K + (double)T * N_out);
   }
   double attn_bytes() const {
     // K and V of every visible slot of each request read once + qkv in + out
@@ -754,7 +758,8 @@ struct LlamaGPU : public ffmi_model {
     // (non-blocking) stream first in every branch
     if (stream) FFMI_HIP(hipStreamSynchronize(stream));
     if (kind == FFMI_FAULT_TP_HEAD_SWAP) {
-      if (w8) return refuse("w8: the head-swap fault repacks fp16 weights");
+      if (wq) return refuse(w4 ? "w4: the head-swap fault repacks fp16 weights"
+                              : "w8: the head-swap fault repacks fp16 weights");
       FFMI_CHECK(layer >= -1 && layer < c.num_layers && heads_l >= 2 && d % 16 == 0,
                  FFMI_ERR_INVALID);
       for (int l = 0; l < c.num_layers; ++l)
@@ -896,11 +901,14 @@ struct LlamaGPU : public ffmi_model {
     if (w8 && (P > 1 || lora)) return refuse("w8: tp_size 1, without LoRA adapters");
     if (w8 && (H % 64 || Hl % 64 || Fl % 64))
       return refuse("w8: hidden, heads * head_dim and intermediate must be multiples of 64");
+    if (w4 && (P > 1 || lora)) return refuse("w4: tp_size 1, without LoRA adapters");
+    if (w4 && (H % 128 || Hl % 128 || Fl % 128))
+      return refuse("w4: hidden, heads * head_dim and intermediate must be multiples of 128");
     FFMI_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
     Tm = (o.max_tokens + 15) & ~15;
-    packed = !w8 && H % 32 == 0 && Hl % 32 == 0 && Fl % 32 == 0;
+    packed = !wq && H % 32 == 0 && Hl % 32 == 0 && Fl % 32 == 0;
     {
-      const double streamed = (w8 ? 1.0 : 2.0) *
+      const double streamed = (w4 ? 0.53125 : w8 ? 1.0 : 2.0) *
                               (c.num_layers * (((double)Nqkv + Hl) * H + 3.0 * Fl * H) + (double)V * H);
       wstream = streamed > 192.0 * (1 << 20) ? FFMI_W_STREAM : 0;
       if (const char *e = getenv("FFMI_W_STREAM"))  // A/B override: 0 / 1
@@ -928,7 +936,7 @@ struct LlamaGPU : public ffmi_model {
                                      3 * ffmi::lora_workspace_bytes(Tm, H)}) + 3) / 4));
     }
     // (a GQA handle does not fold the o projection in: the GEMM runs)
-    fuse_ao = !native_gqa && !kv_fp8 && !w8 && P == 1 && d == 64 && H <= 1024 && H % 16 == 0 &&
+    fuse_ao = !native_gqa && !kv_fp8 && !wq && P == 1 && d == 64 && H <= 1024 && H % 16 == 0 &&
               !(getenv("FFMI_FUSE_AO") && atoi(getenv("FFMI_FUSE_AO")) == 0);
     if (fuse_ao) {  // decode / beam steps (<= 64 rows); prefill blocks run the GEMM
       oslab_T = std::min(Tm, 64);
@@ -978,7 +986,12 @@ struct LlamaGPU : public ffmi_model {
                              ffmi::gemm_w8_onepass_workspace_bytes(Tm, H, Hl, 0),
                              ffmi::gemm_w8_onepass_workspace_bytes(Tm, H, Fl, 0),
                              ffmi::gemm_w8_onepass_workspace_bytes(Tm, Vl, H, 0)});
-      for (int t = 16; t <= Tm && !w8; t += 16) {
+      if (w4)  // (one pass per 64 rows: the slabs of one pass)
+        ws_bytes = std::max({ffmi::gemm_w4_workspace_bytes(Tm, Nqkv, H, 0),
+                             ffmi::gemm_w4_workspace_bytes(Tm, H, Hl, 0),
+                             ffmi::gemm_w4_workspace_bytes(Tm, H, Fl, 0),
+                             ffmi::gemm_w4_workspace_bytes(Tm, Vl, H, 0)});
+      for (int t = 16; t <= Tm && !wq; t += 16) {
         const size_t w1 = ffmi_linear_workspace_bytes(t, Nqkv, H, FFMI_EPI_NONE);
         const size_t w2 = ffmi_linear_workspace_bytes(t, H, Hl, FFMI_EPI_NONE);
         const size_t w3 = ffmi_linear_workspace_bytes(t, Fl, H, FFMI_EPI_SILU_MUL);
@@ -1034,12 +1047,17 @@ struct LlamaGPU : public ffmi_model {
       return FFMI_OK;
     };
     // a linear weight of `ntiles` 16-row tiles: packed fp16, or (w8) bytes and
-    // scales quantised straight from the row-major staging -- the fp16 tiles
-    // are never made
+    // scales, or (w4) nibbles and scale bytes, quantised straight from the
+    // row-major staging -- the fp16 tiles are never made
     auto linear_alloc = [&](uint16_t **w16, uint8_t **q8, float **sc, int ntiles, int K) -> ffmi_status {
-      if (!w8) {
+      if (!wq) {
         wbytes += (size_t)ntiles * ((K + 31) / 32) * 1024;
         return alloc(w16, (size_t)ntiles * ((K + 31) / 32) * 512);
+      }
+      if (w4) {  // (the scale bytes live behind the float pointer)
+        wbytes += (size_t)ntiles * (K / 128) * (1024 + 64);
+        TRY(alloc(q8, (size_t)ntiles * (K / 128) * 1024));
+        return alloc(sc, (size_t)ntiles * (K / 128) * 16);
       }
       wbytes += (size_t)ntiles * (K / 64) * 1024 + (size_t)ntiles * 16 * sizeof(float);
       TRY(alloc(q8, (size_t)ntiles * (K / 64) * 1024));
@@ -1048,6 +1066,9 @@ struct LlamaGPU : public ffmi_model {
     auto linear_pack = [&](const uint16_t *src, int ld, int row0, int col0, int N, int K,
                            uint16_t *w16, uint8_t *q8, float *sc, int step, int off,
                            int pitch) -> hipError_t {
+      if (w4)
+        return ffmi::launch_w4_quantize_pack(src + (size_t)row0 * ld + col0, ld, N, K, q8,
+                                             reinterpret_cast<uint8_t *>(sc), step, off, pitch, stream);
       if (w8)  // (tp_size 1: row0 = col0 = 0)
         return ffmi::launch_w8_quantize_pack(src + (size_t)row0 * ld + col0, ld, N, K, q8, sc, step,
                                              off, pitch, stream);
@@ -1484,7 +1505,7 @@ struct LlamaGPU : public ffmi_model {
     static const int marker_h = getenv("FFMI_MARKERS") ? atoi(getenv("FFMI_MARKERS")) : 0;
     static const int marker_t = getenv("FFMI_MARKERS_T") ? atoi(getenv("FFMI_MARKERS_T")) : 0;
     int mark_i = 0;
-    const bool fuse = (fuse_norms == 2 || (fuse_norms == 1 && H >= 2048)) && !dbg && !w8 &&
+    const bool fuse = (fuse_norms == 2 || (fuse_norms == 1 && H >= 2048)) && !dbg && !wq &&
                       o.tp_size == 1 && T <= 32 && H % 32 == 0 && Hl % 32 == 0 && H <= 4096;
     // (FFMI_MODEL_LORA, the modules of the step's route, lora_route.  down: it
     // runs unfused and its split-K slabs are reduced into proj for the update,
@@ -1518,6 +1539,11 @@ struct LlamaGPU : public ffmi_model {
         if (X != h || !norm8) FFMI_HIP(ffmi::launch_quantize_rows_fp8(X, T, K, x8, x8_s, stream));
         FFMI_HIP(ffmi::launch_gemm_w8a8(x8, x8_s, W, sc, Y, ws, ws_bytes, T, N, K, epi | wstream,
                                         stream));
+        return FFMI_OK;
+      }
+      if (w4) {
+        FFMI_HIP(ffmi::launch_gemm_w4(X, W, reinterpret_cast<const uint8_t *>(sc), Y, ws, ws_bytes, T,
+                                      N, K, epi | wstream, stream));
         return FFMI_OK;
       }
       FFMI_HIP(ffmi::launch_gemm_w8(X, W, sc, Y, ws, ws_bytes, T, N, K, epi | wstream, stream));
@@ -1583,7 +1609,7 @@ struct LlamaGPU : public ffmi_model {
       pr = prof_begin(on);
       ffmi::Partials qkv_part;
       // (a GQA handle takes fp16 qkv rows: a split-K plan runs its reduce pass)
-      if (w8) TRY(gemm8(h, L.qkv8, L.qkv_s, qkv, Nqkv, H, FFMI_EPI_NONE));
+      if (wq) TRY(gemm8(h, L.qkv8, L.qkv_s, qkv, Nqkv, H, FFMI_EPI_NONE));
       else
       FFMI_HIP(ffmi::launch_gemm(fz_in ? res : h, L.wqkv, qkv, (float *)ws, ws_bytes, T, Nqkv, H,
                                  fz_in ? wstream : XP, stream,
@@ -1624,7 +1650,7 @@ struct LlamaGPU : public ffmi_model {
         mk();
       } else if (o.tp_size == 1 || solo) {
         pr = prof_begin(on);
-        if (w8) TRY(gemm8(att, L.o8, L.o_s, proj, H, Hl, FFMI_EPI_NONE));
+        if (wq) TRY(gemm8(att, L.o8, L.o_s, proj, H, Hl, FFMI_EPI_NONE));
         else
         FFMI_HIP(ffmi::launch_gemm(att, L.wo, proj, (float *)ws, ws_bytes, T, H, Hl, XP, stream,
                                    H <= 8192 ? &o_part : nullptr));
@@ -1663,7 +1689,7 @@ struct LlamaGPU : public ffmi_model {
       if (dbg) TRY(dbg_copy(FFMI_DBG_FFN_NORM, l, h, T));
       pr = prof_begin(on);
       const int YP = packed ? FFMI_Y_PACKED : 0;
-      if (w8)
+      if (wq)
         TRY(gemm8(h, L.gu8, L.gu_s, mlp, Fl, H, FFMI_EPI_SILU_MUL));
       else if (fuse_o)
         FFMI_HIP(ffmi::launch_gemm(res, L.wgu, mlp, (float *)ws, ws_bytes, T, Fl, H,
@@ -1682,7 +1708,7 @@ struct LlamaGPU : public ffmi_model {
         mk();
       } else if (o.tp_size == 1 || solo) {
         pr = prof_begin(on);
-        if (w8) TRY(gemm8(mlp, L.d8, L.d_s, proj, H, Fl, FFMI_EPI_NONE));
+        if (wq) TRY(gemm8(mlp, L.d8, L.d_s, proj, H, Fl, FFMI_EPI_NONE));
         else
         FFMI_HIP(ffmi::launch_gemm(mlp, L.wd, proj, (float *)ws, ws_bytes, T, H, Fl, XP, stream,
                                    H <= 8192 ? &down_part : nullptr));
@@ -1739,7 +1765,7 @@ struct LlamaGPU : public ffmi_model {
       dbg_T = T;
     }
     pr = prof_begin(ptail);
-    if (w8) TRY(gemm8(h, lm8, lm_s, logits, Vl, H, FFMI_EPI_NONE));
+    if (wq) TRY(gemm8(h, lm8, lm_s, logits, Vl, H, FFMI_EPI_NONE));
     else TRY(ffmi_linear_ws(h, lm, logits, T, Vl, H, FFMI_EPI_NONE | XP, ws, ws_bytes, s));
     prof_end(pr, GEMM_LM_HEAD, gemm_bytes(T, Vl, Vl, H), 2.0 * T * Vl * H);
     mkt();
@@ -1961,6 +1987,8 @@ ffmi_status create_llama_gpu(const ffmi_llama_config *cfg, const ffmi_model_opts
   m->kv_fp8 = (flags & FFMI_MODEL_KV_FP8) != 0;
   m->w8 = (flags & FFMI_MODEL_W8) != 0;
   m->a8 = m->w8 && (flags & FFMI_MODEL_A8) != 0;
+  m->w4 = (flags & FFMI_MODEL_W4) != 0;
+  m->wq = m->w8 || m->w4;
   if (m->lora && (o->mode == FFMI_MODEL_BEAM || o->tp_size > 1)) {
     delete m;
     ffmi_set_last_error("lora: INC / TREE models at tp_size 1", __FILE__, __LINE__);

@@ -41,6 +41,7 @@ MODEL_LORA = 4  # (2 is left unassigned: it stays an invalid flag)
 MODEL_KV_FP8 = 16  # (8, like 2, is left unassigned: it stays an invalid flag)
 MODEL_W8 = 32  # fp8 (e4m3) weight-only linear layers
 MODEL_A8 = 128  # with MODEL_W8: fp8 activations, one dynamic scale per token
+MODEL_W4 = 256  # OCP MXFP4 weight-only linear layers
 ATTN_KV_FP8 = 1  # ffmi_attn_create_ex flag: an 8-bit (e4m3) KV cache
 LORA_MAX_ADAPTERS, LORA_MAX_RANK = 8, 64
 # FFMI_LORA_Q .. FFMI_LORA_DOWN by the HF module name (masks: 1 << id); gate_proj
@@ -192,6 +193,16 @@ SIGNATURES = {
     "ffmi_linear_w8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                c_void_p, c_size_t, c_void_p]),
     "ffmi_debug_linear_w8_unpack": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "ffmi_linear_w4_packed_bytes": (c_size_t, [c_int, c_int]),
+    "ffmi_linear_w4_scale_bytes": (c_size_t, [c_int, c_int]),
+    "ffmi_linear_w4_quantize_pack": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "ffmi_linear_w4_quantize_pack_gate_up": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                                     c_void_p, c_void_p]),
+    "ffmi_linear_w4_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "ffmi_linear_w4": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                               c_void_p, c_size_t, c_void_p]),
+    "ffmi_debug_linear_w4_unpack": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
+                                            c_void_p, c_void_p]),
     "ffmi_quantize_rows_fp8": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "ffmi_rmsnorm_fp8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                  c_int, c_float, c_void_p]),

@@ -58,13 +58,17 @@ class Model:
         keep e4m3 bytes with one fp32 scale per output channel and run the
         fp8-weight GEMM (FFMI_MODEL_W8: about half the weight bytes, see
         weight_bytes; any mode, with native_gqa and kv_cache_dtype="fp8"; not
-        full_precision, tp_size > 1 or lora); "fp16" is the default model.
+        full_precision, tp_size > 1 or lora); "mxfp4": OCP MXFP4 nibbles with
+        one power-of-two scale byte per 32 input columns and the W4A16 GEMM
+        (FFMI_MODEL_W4: about 0.27 of the fp16 weight bytes; as "fp8", and
+        hidden, heads * head_dim and intermediate multiples of 128); "fp16" is
+        the default model.
         activation_dtype "fp8" (with weight_dtype "fp8" only): every linear
         layer's input is e4m3 with one dynamic scale per token and runs on the
         fp8 matrix instruction (FFMI_MODEL_A8); the residual stream, attention
         and logits stay fp16."""
-        if weight_dtype not in ("fp16", "fp8"):
-            raise ValueError(f"weight_dtype {weight_dtype!r}: 'fp16' or 'fp8'")
+        if weight_dtype not in ("fp16", "fp8", "mxfp4"):
+            raise ValueError(f"weight_dtype {weight_dtype!r}: 'fp16', 'fp8' or 'mxfp4'")
         if activation_dtype not in ("fp16", "fp8"):
             raise ValueError(f"activation_dtype {activation_dtype!r}: 'fp16' or 'fp8'")
         if activation_dtype == "fp8" and weight_dtype != "fp8":
@@ -88,6 +92,7 @@ class Model:
                                        (F.MODEL_LORA if lora else 0) |
                                        (F.MODEL_KV_FP8 if fp8 else 0) |
                                        (F.MODEL_W8 if weight_dtype == "fp8" else 0) |
+                                       (F.MODEL_W4 if weight_dtype == "mxfp4" else 0) |
                                        (F.MODEL_A8 if activation_dtype == "fp8" else 0),
                                        ctypes.byref(h)),
                 "ffmi_model_create")
@@ -102,7 +107,8 @@ class Model:
 
     def weight_bytes(self) -> int:
         """Resident bytes of the linear-layer weights (ffmi_model_weight_bytes):
-        packed fp16, or bytes plus scales under weight_dtype="fp8"."""
+        packed fp16, bytes plus scales under weight_dtype="fp8", nibbles plus
+        scale bytes under "mxfp4"."""
         return int(F.lib().ffmi_model_weight_bytes(self.handle))
 
     def set_sampling(self, generation_config: Optional[GenerationConfig], seed: int = 0):

@@ -295,6 +295,53 @@ ffmi_status ffmi_debug_linear_w8_plan(int T, int out_dim, int in_dim, int epilog
 ffmi_status ffmi_debug_linear_w8_unpack(const void *W8_packed, int out_dim, int in_dim,
                                         int gate_up, void *bytes_out, ffmi_stream stream);
 
+/* OCP MXFP4 weight-only linear layers (kernels/gemm_w4.hip), W4A16:
+ *   Y[t][n] = sum_k X[t][k] * deq[n][k],  deq[n][k] = e2m1(nibble[n][k]) * 2^e,
+ * X / Y row-major fp16, fp32 accumulation; one e8m0 scale byte e + 127 per 32
+ * consecutive k of a row (4.25 bits per weight).  in_dim % 128 == 0 (else
+ * FFMI_ERR_UNSUPPORTED).  The quantiser, per block of row n, columns 32b ..
+ * 32b + 31:
+ *   amax = the largest |W| of the block (fp32); amax == 0: e = 0; otherwise
+ *   e = max(floor(log2(amax)) - 2, -12) (fp16 sources: e <= 13, so no upper
+ *   clamp); the scale byte is e + 127, and 0xFF is never written.
+ *   v = W / 2^e (exact in fp32); |v| is rounded to the nearest of {0, 0.5, 1,
+ *   1.5, 2, 3, 4, 6} = codes 0..7, a tie to the code with an even low bit
+ *   (0.25 -> 0, 0.75 -> 1, 1.25 -> 1, 1.75 -> 2, 2.5 -> 2, 3.5 -> 4, 5 -> 4),
+ *   above 6 to 6.  nibble = sign << 3 | code, sign the source's sign bit.
+ *   The lower clamp keeps every nonzero deq at least 2^-13, a normal f16:
+ *   widening at scale 2^e is exact.  A block whose amax is below 2^-10 loses
+ *   precision by that clamp; that is the rule.
+ *   packed nibbles: 16 x 128 quad blocks of 1 KiB, K-major; scales: 64 bytes
+ *   per quad block (4 per row), K-major; out_dim padded to 16 with zero
+ *   nibbles and scale byte 127.  The _gate_up form interleaves gate and up
+ *   tiles (2i, 2i+1) in both arrays for FFMI_EPI_SILU_MUL: 2 * packed_bytes
+ *   and 2 * scale_bytes.
+ *   ffmi_linear_w4: epilogue FFMI_EPI_NONE or FFMI_EPI_SILU_MUL, optionally |
+ *   FFMI_W_STREAM; FFMI_X_PACKED / FFMI_Y_PACKED: FFMI_ERR_UNSUPPORTED.  One
+ *   kernel, T <= 64 rows per launch; more rows run one weight pass per 64
+ *   rows.  A row's result does not depend on T or on the rows around it.
+ *   workspace: at least ffmi_linear_w4_workspace_bytes (split-K slabs for
+ *   min(T, 64) rows; 0 for shapes that do not split K); too small, a NULL
+ *   pointer, T < 0: FFMI_ERR_INVALID.
+ * Every refusal leaves a message naming "w4" in ffmi_last_error. */
+size_t ffmi_linear_w4_packed_bytes(int out_dim, int in_dim);
+size_t ffmi_linear_w4_scale_bytes(int out_dim, int in_dim);
+ffmi_status ffmi_linear_w4_quantize_pack(const void *W_f16, int out_dim, int in_dim,
+                                         void *W4_packed, void *scales, ffmi_stream stream);
+ffmi_status ffmi_linear_w4_quantize_pack_gate_up(const void *Wg_f16, const void *Wu_f16,
+                                                 int out_dim, int in_dim, void *W4_packed,
+                                                 void *scales, ffmi_stream stream);
+size_t ffmi_linear_w4_workspace_bytes(int T, int out_dim, int in_dim, int epilogue);
+ffmi_status ffmi_linear_w4(const void *X, const void *W4_packed, const void *scales, void *Y,
+                           int T, int out_dim, int in_dim, int epilogue, void *workspace,
+                           size_t workspace_bytes, ffmi_stream stream);
+/* Test hook: row-major [out_dim][in_dim] nibble values, one per byte, and
+ * [out_dim][in_dim / 32] scale bytes of a packed pair; gate_up 0: plain
+ * buffers, 1 / 2: the gate / up matrix of _gate_up buffers. */
+ffmi_status ffmi_debug_linear_w4_unpack(const void *W4_packed, const void *scales, int out_dim,
+                                        int in_dim, int gate_up, void *nibbles_out,
+                                        void *scales_out, ffmi_stream stream);
+
 /* W8A8 (kernels/gemm_w8a8.hip): the packed fp8 weights above against fp8
  * (e4m3) activations with one dynamic fp32 scale per token, on the fp8 matrix
  * instruction (fp32 accumulation; products of two e4m3 values are exact):
@@ -706,8 +753,21 @@ ffmi_status ffmi_model_set_kv_scales(ffmi_model *m, float k_scale, float v_scale
  *   ffmi_last_error); W8's refusals carry over.
  *   (bit value 128: 64, like 2 and 8, stays an unknown flag, FFMI_ERR_INVALID) */
 #define FFMI_MODEL_A8 128u
-/* resident bytes of the linear-layer weights (this rank's; packed fp16, or
- * bytes plus scales under FFMI_MODEL_W8); 0 for a model that does not report */
+/*   FFMI_MODEL_W4: the linear layers keep OCP MXFP4 nibbles with one e8m0
+ *   scale byte per 32 k (ffmi_linear_w4_quantize_pack, applied to every weight
+ *   right after its fp16 form is made); only nibbles and scale bytes stay
+ *   resident, about 0.27 of the fp16 model's ffmi_model_weight_bytes.  The
+ *   step is FFMI_MODEL_W8's with every GEMM ffmi_linear_w4.  All three modes,
+ *   with FFMI_MODEL_NATIVE_GQA and FFMI_MODEL_KV_FP8, eager and under graph
+ *   replay.  FFMI_ERR_UNSUPPORTED ("w4" in ffmi_last_error): together with
+ *   FFMI_MODEL_W8 or FFMI_MODEL_A8, full_precision, tp_size > 1,
+ *   FFMI_MODEL_LORA, hidden, heads * head_dim or intermediate not a multiple
+ *   of 128.
+ *   (bit value 256; 2, 8 and 64 stay unknown flags) */
+#define FFMI_MODEL_W4 256u
+/* resident bytes of the linear-layer weights (this rank's; packed fp16, bytes
+ * plus scales under FFMI_MODEL_W8, nibbles plus scale bytes under
+ * FFMI_MODEL_W4); 0 for a model that does not report */
 size_t ffmi_model_weight_bytes(ffmi_model *m);
 /* LoRA adapters of a FFMI_MODEL_LORA model.  Adapter ids are process-wide
  * (0 .. FFMI_LORA_MAX_ADAPTERS - 1): a request names one at registration
@@ -1177,7 +1237,10 @@ const char *ffmi_last_error(void);
  * ffmi_model_weight_bytes; and its M-split kernel for 65 .. 256 rows:
  * ffmi_linear_w8_onepass_workspace_bytes, ffmi_debug_linear_w8_plan; and fp8
  * activations with per-token scales (W8A8): ffmi_quantize_rows_fp8,
- * ffmi_rmsnorm_fp8, ffmi_linear_w8a8(_workspace_bytes), FFMI_MODEL_A8 */
+ * ffmi_rmsnorm_fp8, ffmi_linear_w8a8(_workspace_bytes), FFMI_MODEL_A8; and
+ * MXFP4 weight-only linear layers: ffmi_linear_w4(_packed_bytes, _scale_bytes,
+ * _quantize_pack(_gate_up), _workspace_bytes), ffmi_debug_linear_w4_unpack,
+ * FFMI_MODEL_W4 */
 const char *ffmi_version(void);
 
 #ifdef __cplusplus

@@ -40,6 +40,14 @@ ffmi_rmsnorm, H = 4096), and the serving part with weight_dtype "fp8" against
 "fp8" + activation_dtype "fp8".
 
     python scripts/linear_w8_bench.py --a8 [--out profiles/linear_w8a8_bench.json]
+
+--w4: OCP MXFP4 weights (ffmi_linear_w4).  The same five shapes, cold-weight
+protocol and method at T = 8, 32 and 168, three legs alternating in one
+process: "mxfp4" (one pass per 64 rows: three at T = 168; each weight copy has
+its own scale bytes), "fp8" (ffmi_linear_w8 with its one-pass workspace) and
+"fp16".  Then the serving part with weight_dtype "fp16", "fp8" and "mxfp4".
+
+    python scripts/linear_w8_bench.py --w4 [--out profiles/linear_w4_bench.json]
 """
 import argparse
 import ctypes
@@ -223,6 +231,59 @@ def a8_rows(args):
     return rows, norms
 
 
+def w4_rows(args):
+    L, rng, rows = F.lib(), np.random.default_rng(0), []
+    block16 = f16(rng.standard_normal(8 << 20) * 0.02)
+    block8 = rng.integers(0, 127, size=16 << 20).astype(np.uint8) | \
+        (rng.integers(0, 2, size=16 << 20).astype(np.uint8) << 7)  # (no NaN byte)
+    block4 = rng.integers(0, 256, size=16 << 20).astype(np.uint8)  # (every nibble is a value)
+    for name, N, K, epi in SHAPES:
+        g = 2 if epi == F.EPI_SILU_MUL else 1
+        b16, b8 = g * L.ffmi_linear_packed_bytes(N, K), g * L.ffmi_linear_w8_packed_bytes(N, K)
+        b4, bs4 = g * L.ffmi_linear_w4_packed_bytes(N, K), g * L.ffmi_linear_w4_scale_bytes(N, K)
+        (w16, n16), (w8, n8), (w4, n4) = copies(b16, block16), copies(b8, block8), copies(b4, block4)
+        sc8 = Buf(np.full(g * L.ffmi_linear_w8_scale_count(N), 2.0**-6, np.float32))
+        sc4 = Buf(np.full(n4 * bs4, 127 - 6, np.uint8))  # (a copy of the scale bytes per weight copy)
+        for T in [int(t) for t in args.T.split(",")]:
+            X = Buf(f16(rng.standard_normal((T, K))))
+            Xp = Buf.empty((L.ffmi_packed_activation_bytes(T, K),), np.uint8)
+            F.check(L.ffmi_pack_activations(X.ptr, T, K, Xp.ptr, None))
+            Y = Buf.empty((T, N), np.float16)
+            nws = max(L.ffmi_linear_workspace_bytes(T, N, K, epi), 16,
+                      L.ffmi_linear_w8_onepass_workspace_bytes(T, N, K, epi),
+                      L.ffmi_linear_w4_workspace_bytes(T, N, K, epi))
+            ws, it = Buf.empty((nws,), np.uint8), [0]
+
+            def wt(base, n, b):
+                return ctypes.c_void_p(base.ptr.value + (it[0] % n) * b)
+
+            def mxfp4(n):
+                for _ in range(n):
+                    it[0] += 1
+                    F.check(L.ffmi_linear_w4(X.ptr, wt(w4, n4, b4), wt(sc4, n4, bs4), Y.ptr, T, N, K,
+                                             epi | F.W_STREAM, ws.ptr, nws, None))
+
+            def fp8(n):
+                for _ in range(n):
+                    it[0] += 1
+                    F.check(L.ffmi_linear_w8(X.ptr, wt(w8, n8, b8), sc8.ptr, Y.ptr, T, N, K,
+                                             epi | F.W_STREAM, ws.ptr, nws, None))
+
+            def fp16(n):
+                for _ in range(n):
+                    it[0] += 1
+                    F.check(L.ffmi_linear_ws(Xp.ptr, wt(w16, n16, b16), Y.ptr, T, N, K,
+                                             epi | F.X_PACKED | F.W_STREAM, ws.ptr, nws, None))
+            res, block = timed_legs(args, dict(mxfp4=mxfp4, fp8=fp8, fp16=fp16))
+            row = dict(gemm=name, T=T, N=N, K=K, rounds=args.rounds, calls_per_block=block,
+                       weight_bytes=dict(mxfp4=int(b4 + bs4), fp8=int(b8), fp16=int(b16)), **res)
+            row["fp8_over_mxfp4"] = round(res["fp8"]["us"] / res["mxfp4"]["us"], 3)
+            row["fp16_over_mxfp4"] = round(res["fp16"]["us"] / res["mxfp4"]["us"], 3)
+            print(json.dumps(row), flush=True)
+            rows.append(row)
+    return rows
+
+
 def mid_worker():
     """stdin: one JSON command per line -- {"shape": i} (weight copies of SHAPES[i]),
     {"T": t} (activations, output, workspace), {"leg": l, "n": n} (n calls); stdout:
@@ -331,7 +392,7 @@ def serve(args):
     rm_kw = dict(max_requests_per_batch=B, max_tokens_per_batch=1024, max_sequence_length=512)
     prompts = make_prompts(B, P - 1, cfg["vocab_size"])
     kinds = {"fp8": dict(weight_dtype="fp8"), "fp8_a8": dict(weight_dtype="fp8", activation_dtype="fp8")} \
-        if args.a8 else {d: dict(weight_dtype=d) for d in ("fp16", "fp8")}
+        if args.a8 else {d: dict(weight_dtype=d) for d in ("fp16", "fp8") + (("mxfp4",) if args.w4 else ())}
     models = {d: fa.Model(cfg, "inc", max_requests=B, max_tokens=1024, max_seq_len=512,
                           weight_seed=20250117, **kw) for d, kw in kinds.items()}
 
@@ -352,6 +413,8 @@ def serve(args):
                generates_per_window=args.generates, tokens_per_s=rates, median=med,
                **({"fp8_a8_over_fp8": round(med["fp8_a8"] / med["fp8"], 4)} if args.a8 else
                   {"fp8_over_fp16": round(med["fp8"] / med["fp16"], 4)}),
+               **({"mxfp4_over_fp16": round(med["mxfp4"] / med["fp16"], 4),
+                   "mxfp4_over_fp8": round(med["mxfp4"] / med["fp8"], 4)} if args.w4 else {}),
                weight_bytes={d: m.weight_bytes() for d, m in models.items()})
     print(json.dumps(out), flush=True)
     return out
@@ -361,6 +424,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mid", action="store_true", help="the M-split kernel's three legs")
     ap.add_argument("--a8", action="store_true", help="the W8A8 legs")
+    ap.add_argument("--w4", action="store_true", help="the MXFP4 legs")
     ap.add_argument("--mid-worker", action="store_true", help="(a --mid run's child process)")
     ap.add_argument("--T", default=None, help="default 8,32,168; --mid: 72,128,168,256")
     ap.add_argument("--rounds", type=int, default=5)
@@ -380,6 +444,17 @@ def main():
         if args.serve:
             res["serving"] = serve(args)
         out = args.out.replace("linear_w8_bench.json", "linear_w8a8_bench.json")
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        with open(out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+        return
+    if args.w4:
+        fa.set_device(0)
+        res = dict(bench="linear_w4_bench", gemms=w4_rows(args))
+        if args.serve:
+            res["serving"] = serve(args)
+        out = args.out.replace("linear_w8_bench.json", "linear_w4_bench.json")
         os.makedirs(os.path.dirname(out), exist_ok=True)
         with open(out, "w") as f:
             json.dump(res, f, indent=1)
