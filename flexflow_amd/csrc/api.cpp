@@ -824,6 +824,22 @@ extern "C" size_t ffmi_linear_w4_workspace_bytes(int T, int out_dim, int in_dim,
   return ffmi::gemm_w4_workspace_bytes(T, out_dim, in_dim, epilogue);
 }
 
+extern "C" size_t ffmi_linear_w4_onepass_workspace_bytes(int T, int out_dim, int in_dim,
+                                                         int epilogue) {
+  return ffmi::gemm_w4_onepass_workspace_bytes(T, out_dim, in_dim, epilogue);
+}
+
+extern "C" ffmi_status ffmi_debug_linear_w4_plan(int T, int out_dim, int in_dim, int epilogue,
+                                                 size_t workspace_bytes, int *plan) {
+  FFMI_W4_CHECK(plan && T > 0 && out_dim > 0 && in_dim > 0, FFMI_ERR_INVALID,
+                "null plan, T <= 0 or an empty matrix");
+  FFMI_W4_CHECK(in_dim % 128 == 0, FFMI_ERR_UNSUPPORTED, "in_dim % 128 != 0");
+  const ffmi::W4Launch l = ffmi::plan_w4_launch(T, out_dim, in_dim, epilogue, workspace_bytes);
+  plan[0] = l.path, plan[1] = l.MTW, plan[2] = l.NTW, plan[3] = l.S, plan[4] = l.passes;
+  plan[5] = l.nblk;
+  return FFMI_OK;
+}
+
 extern "C" ffmi_status ffmi_linear_w4(const void *X, const void *W4_packed, const void *scales,
                                       void *Y, int T, int out_dim, int in_dim, int epilogue,
                                       void *workspace, size_t workspace_bytes,

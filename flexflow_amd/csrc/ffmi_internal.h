@@ -407,7 +407,17 @@ struct W4Plan {
 W4Plan plan_w4(int N, int K, int epilogue);
 size_t w4_packed_bytes(int N, int K);
 size_t w4_scale_bytes(int N, int K);
-size_t gemm_w4_workspace_bytes(int T, int N, int K, int epilogue);  // slabs for min(T, 64) rows
+size_t gemm_w4_workspace_bytes(int T, int N, int K, int epilogue);  // the minimum: 64 rows of slabs
+// what lets rows above 64 take the M-split kernel (kernels/gemm_w4_mid.hip):
+// slabs for min(T, 256) rows; 0 for a shape that does not split K
+size_t gemm_w4_onepass_workspace_bytes(int T, int N, int K, int epilogue);
+// The launch plan of (T, N, K, epilogue) with ws_bytes of workspace, with
+// W8Launch's fields: path 0 the skinny kernel, 1 the M-split kernel -- of the
+// first pass; a last pass of <= 64 rows is always a skinny launch.
+struct W4Launch {
+  int path = 0, MTW = 0, NTW = 0, S = 1, passes = 0, nblk = 0, rows = 0;  // rows: per pass
+};
+W4Launch plan_w4_launch(int T, int N, int K, int epilogue, size_t ws_bytes);
 // rows [0, N) of a row-major fp16 matrix (row stride ld) -> destination tiles
 // tile_step * nt + tile_offset of the nibble and of the scale array
 hipError_t launch_w4_quantize_pack(const uint16_t *src, int ld, int N, int K, uint8_t *dst,
@@ -416,7 +426,7 @@ hipError_t launch_w4_quantize_pack(const uint16_t *src, int ld, int N, int K, ui
 hipError_t launch_w4_unpack(const uint8_t *src, const uint8_t *scales, int N, int K, uint8_t *nib,
                             uint8_t *sc, int tile_step, int tile_offset, int pitch, hipStream_t s);
 // Y [T][N] fp16 rows = X [T][K] . deq^T, epilogue FFMI_EPI_NONE /
-// FFMI_EPI_SILU_MUL (| FFMI_W_STREAM); any T: one pass per 64 rows
+// FFMI_EPI_SILU_MUL (| FFMI_W_STREAM); any T (plan_w4_launch: passes of 256 or 64 rows)
 hipError_t launch_gemm_w4(const uint16_t *X, const uint8_t *W4, const uint8_t *scales, uint16_t *Y,
                           float *ws, size_t ws_bytes, int T, int N, int K, int epilogue,
                           hipStream_t s);

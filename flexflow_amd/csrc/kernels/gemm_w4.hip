@@ -23,16 +23,17 @@
 // k-row of the allocation).  in_dim % 128 == 0; out_dim is padded to 16
 // (padding rows: zero nibbles, scale byte 127).
 //
-// The GEMM (T <= 64 rows per launch; more rows run one pass per 64 rows --
-// there is no M-split W4 kernel) follows gemm_w8_kernel: 4 waves, wave w owns
-// kW4NT adjacent n-tiles, gridDim.y = S splits K (plan_w4: a function of (N,
-// K, epilogue), never of T); weights and scales go from global memory straight
-// to registers through a ring kW4Ring quad blocks deep per tile, non-temporal
-// under FFMI_W_STREAM; the activation chunk (MT*16 rows x 128 k) is loaded
-// cooperatively through the same ring, staged in a double-buffered LDS tile in
-// A-fragment order (MT * 8 KiB per buffer pair) and read by every wave with
-// 16-byte LDS reads; D = W_tile . X_tile^T, a lane holds 4 consecutive output
-// columns of one row.
+// The GEMM of this file (T <= 64 rows per launch: the decode regime;
+// gemm_w4_mid.hip holds the M-split kernel for 65 .. 256 rows, with the same
+// numerics per row, and plan_w4_launch below chooses between them) follows
+// gemm_w8_kernel: 4 waves, wave w owns kW4NT adjacent n-tiles, gridDim.y = S
+// splits K (plan_w4: a function of (N, K, epilogue), never of T); weights and
+// scales go from global memory straight to registers through a ring kW4Ring
+// quad blocks deep per tile, non-temporal under FFMI_W_STREAM; the activation
+// chunk (MT*16 rows x 128 k) is loaded cooperatively through the same ring,
+// staged in a double-buffered LDS tile in A-fragment order (MT * 8 KiB per
+// buffer pair) and read by every wave with 16-byte LDS reads; D = W_tile .
+// X_tile^T, a lane holds 4 consecutive output columns of one row.
 //
 // kW4NT = 2, kW4Ring = 6: 4 waves x 2 x 6 KiB = 48 KiB of weight loads in
 // flight per workgroup, gemm_w8_kernel's figure.  X covers twice the k per
@@ -56,28 +57,11 @@
 // (four MFMAs each, in k order), then slices 0..S-1 (launch_partials_reduce)
 // -- fixed by (N, K, epilogue).
 #include <algorithm>
+#include <cstdlib>
 
-#include "gemm_w8.h"
+#include "gemm_w4.h"
 
 namespace ffmi {
-
-constexpr int kW4NT = 2;    // n-tiles per wave (even: a gate tile and its up tile)
-constexpr int kW4Ring = 6;  // quad blocks in flight per tile and wave
-constexpr int kW4Rows = 64;  // rows per launch
-constexpr int kW4MaxS = 8;
-constexpr int kW4MinSteps = 2;  // quad steps a k-slice keeps at least
-constexpr int kW4Groups = 256;  // workgroups the plan aims for (one per CU)
-
-// eight e2m1 nibbles of one scale block -> an MFMA f16 fragment, times `scale`
-__device__ __forceinline__ h8 w4_widen(uint32_t q, float scale) {
-  const h2w p0 = __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(q, scale, 0);
-  const h2w p1 = __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(q, scale, 1);
-  const h2w p2 = __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(q, scale, 2);
-  const h2w p3 = __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(q, scale, 3);
-  return h8{p0[0], p0[1], p1[0], p1[1], p2[0], p2[1], p3[0], p3[1]};
-}
-// 2^(byte - 127)
-__device__ __forceinline__ float e8m0_f32(uint32_t byte) { return __uint_as_float(byte << 23); }
 
 // T <= MT*16 <= 64 rows; X row-major [T][K], K = 128 KT4; W4 / scales as above
 // (pitch = tiles per k-row of the allocation); EPI 1: tiles (2p, 2p+1) =
@@ -355,7 +339,41 @@ static void launch_w4_rows(const W4Plan &p, bool silu, bool ntl, const uint16_t 
 #undef FFMI_W4
 }
 
-// One launch (and, for a split shape, one reduce) per 64 rows
+size_t gemm_w4_onepass_workspace_bytes(int T, int N, int K, int epilogue) {
+  if (T <= 0 || N <= 0 || K <= 0 || K % 128) return 0;
+  const W4Plan p = plan_w4(N, K, epilogue);
+  return p.S > 1 ? (size_t)p.S * std::min(T, kW4MidRows) * p.ntiles * 16 * sizeof(float) : 0;
+}
+
+// FFMI_W4_MULTIPASS=1: rows above 64 keep one skinny pass per 64 rows, whatever
+// the workspace (A/B against the M-split kernel in one build); once
+static bool sw_w4_multipass() {
+  static const bool v = [] { const char *e = getenv("FFMI_W4_MULTIPASS"); return e && atoi(e) != 0; }();
+  return v;
+}
+
+// The launch plan: what launch_gemm_w4 does and ffmi_debug_linear_w4_plan
+// reports -- plan_w8_launch's rule.  Above 64 rows the M-split kernel
+// (gemm_w4_mid.hip) covers 256 rows per weight pass where the workspace holds
+// its slabs (a shape that does not split K needs none); a split shape given
+// only the minimum, the skinny kernel's 64 rows of slabs, keeps one skinny
+// pass per 64 rows.  The bits are the same.
+W4Launch plan_w4_launch(int T, int N, int K, int epilogue, size_t ws_bytes) {
+  W4Launch l;
+  const W4Plan p = plan_w4(N, K, epilogue);
+  l.path = T > kW4Rows && !sw_w4_multipass() &&
+           ws_bytes >= gemm_w4_onepass_workspace_bytes(T, N, K, epilogue);
+  l.rows = l.path ? kW4MidRows : kW4Rows;
+  const int mt = (std::min(T, l.rows) + 15) / 16;  // m-tiles of the first pass
+  l.MTW = l.path ? std::max(2, (mt + 3) / 4) : mt;
+  l.NTW = l.path ? kW4MidNTW : kW4NT;
+  l.S = p.S, l.passes = (T + l.rows - 1) / l.rows, l.nblk = p.nblk;
+  return l;
+}
+
+// One launch (and, for a split shape, one reduce) per l.rows rows: the M-split
+// kernel for a pass of more than 64 rows, the skinny kernel for a shorter
+// (last) one
 hipError_t launch_gemm_w4(const uint16_t *X, const uint8_t *W4, const uint8_t *scales, uint16_t *Y,
                           float *ws, size_t ws_bytes, int T, int N, int K, int epilogue,
                           hipStream_t s) {
@@ -367,16 +385,22 @@ hipError_t launch_gemm_w4(const uint16_t *X, const uint8_t *W4, const uint8_t *s
   const W4Plan p = plan_w4(N, K, epilogue);
   if (p.S > 1 && (!ws || ws_bytes < gemm_w4_workspace_bytes(T, N, K, epilogue)))
     return hipErrorInvalidValue;
+  const W4Launch l = plan_w4_launch(T, N, K, epilogue, ws ? ws_bytes : 0);
   const bool silu = base == FFMI_EPI_SILU_MUL, ntl = (epilogue & FFMI_W_STREAM) != 0;
-  for (int t0 = 0; t0 < T; t0 += kW4Rows) {
-    const int Tp = std::min(kW4Rows, T - t0);
+  for (int t0 = 0; t0 < T; t0 += l.rows) {
+    const int Tp = std::min(l.rows, T - t0), mt = (Tp + 15) / 16;
     const uint16_t *Xp = X + (size_t)t0 * K;
     uint16_t *Yp = Y + (size_t)t0 * N;
-    switch ((Tp + 15) / 16) {
-      case 1: launch_w4_rows<1>(p, silu, ntl, Xp, W4, scales, Yp, ws, Tp, N, K, s); break;
-      case 2: launch_w4_rows<2>(p, silu, ntl, Xp, W4, scales, Yp, ws, Tp, N, K, s); break;
-      case 3: launch_w4_rows<3>(p, silu, ntl, Xp, W4, scales, Yp, ws, Tp, N, K, s); break;
-      default: launch_w4_rows<4>(p, silu, ntl, Xp, W4, scales, Yp, ws, Tp, N, K, s); break;
+    if (Tp > kW4Rows) {
+      launch_w4_mid_rows(p, std::max(2, (mt + 3) / 4), silu, ntl, Xp, W4, scales, Yp, ws, Tp, N, K,
+                         s);
+    } else {
+      switch (mt) {
+        case 1: launch_w4_rows<1>(p, silu, ntl, Xp, W4, scales, Yp, ws, Tp, N, K, s); break;
+        case 2: launch_w4_rows<2>(p, silu, ntl, Xp, W4, scales, Yp, ws, Tp, N, K, s); break;
+        case 3: launch_w4_rows<3>(p, silu, ntl, Xp, W4, scales, Yp, ws, Tp, N, K, s); break;
+        default: launch_w4_rows<4>(p, silu, ntl, Xp, W4, scales, Yp, ws, Tp, N, K, s); break;
+      }
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;

@@ -986,11 +986,11 @@ struct LlamaGPU : public ffmi_model {
                              ffmi::gemm_w8_onepass_workspace_bytes(Tm, H, Hl, 0),
                              ffmi::gemm_w8_onepass_workspace_bytes(Tm, H, Fl, 0),
                              ffmi::gemm_w8_onepass_workspace_bytes(Tm, Vl, H, 0)});
-      if (w4)  // (one pass per 64 rows: the slabs of one pass)
-        ws_bytes = std::max({ffmi::gemm_w4_workspace_bytes(Tm, Nqkv, H, 0),
-                             ffmi::gemm_w4_workspace_bytes(Tm, H, Hl, 0),
-                             ffmi::gemm_w4_workspace_bytes(Tm, H, Fl, 0),
-                             ffmi::gemm_w4_workspace_bytes(Tm, Vl, H, 0)});
+      if (w4)  // (the same for kernels/gemm_w4_mid.hip)
+        ws_bytes = std::max({ffmi::gemm_w4_onepass_workspace_bytes(Tm, Nqkv, H, 0),
+                             ffmi::gemm_w4_onepass_workspace_bytes(Tm, H, Hl, 0),
+                             ffmi::gemm_w4_onepass_workspace_bytes(Tm, H, Fl, 0),
+                             ffmi::gemm_w4_onepass_workspace_bytes(Tm, Vl, H, 0)});
       for (int t = 16; t <= Tm && !wq; t += 16) {
         const size_t w1 = ffmi_linear_workspace_bytes(t, Nqkv, H, FFMI_EPI_NONE);
         const size_t w2 = ffmi_linear_workspace_bytes(t, H, Hl, FFMI_EPI_NONE);

@@ -199,6 +199,9 @@ SIGNATURES = {
     "ffmi_linear_w4_quantize_pack_gate_up": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p,
                                                      c_void_p, c_void_p]),
     "ffmi_linear_w4_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "ffmi_linear_w4_onepass_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "ffmi_debug_linear_w4_plan": (c_int, [c_int, c_int, c_int, c_int, c_size_t,
+                                          ctypes.POINTER(c_int)]),
     "ffmi_linear_w4": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                c_void_p, c_size_t, c_void_p]),
     "ffmi_debug_linear_w4_unpack": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,

@@ -317,12 +317,16 @@ ffmi_status ffmi_debug_linear_w8_unpack(const void *W8_packed, int out_dim, int 
  *   tiles (2i, 2i+1) in both arrays for FFMI_EPI_SILU_MUL: 2 * packed_bytes
  *   and 2 * scale_bytes.
  *   ffmi_linear_w4: epilogue FFMI_EPI_NONE or FFMI_EPI_SILU_MUL, optionally |
- *   FFMI_W_STREAM; FFMI_X_PACKED / FFMI_Y_PACKED: FFMI_ERR_UNSUPPORTED.  One
- *   kernel, T <= 64 rows per launch; more rows run one weight pass per 64
- *   rows.  A row's result does not depend on T or on the rows around it.
+ *   FFMI_W_STREAM; FFMI_X_PACKED / FFMI_Y_PACKED: FFMI_ERR_UNSUPPORTED.  Two
+ *   kernels: T <= 64 rows, and an M-split one (kernels/gemm_w4_mid.hip) for
+ *   65 .. 256 rows; more rows run one weight pass per 256 rows.  A row's
+ *   result does not depend on T, on the rows around it or on the kernel.
  *   workspace: at least ffmi_linear_w4_workspace_bytes (split-K slabs for
  *   min(T, 64) rows; 0 for shapes that do not split K); too small, a NULL
- *   pointer, T < 0: FFMI_ERR_INVALID.
+ *   pointer, T < 0: FFMI_ERR_INVALID.  With less than
+ *   ffmi_linear_w4_onepass_workspace_bytes (slabs for min(T, 256) rows; 0 for
+ *   shapes that do not split K) a shape that splits K serves T > 64 as one
+ *   pass per 64 rows, each re-reading the weights -- the same bits, slower.
  * Every refusal leaves a message naming "w4" in ffmi_last_error. */
 size_t ffmi_linear_w4_packed_bytes(int out_dim, int in_dim);
 size_t ffmi_linear_w4_scale_bytes(int out_dim, int in_dim);
@@ -332,9 +336,16 @@ ffmi_status ffmi_linear_w4_quantize_pack_gate_up(const void *Wg_f16, const void 
                                                  int out_dim, int in_dim, void *W4_packed,
                                                  void *scales, ffmi_stream stream);
 size_t ffmi_linear_w4_workspace_bytes(int T, int out_dim, int in_dim, int epilogue);
+size_t ffmi_linear_w4_onepass_workspace_bytes(int T, int out_dim, int in_dim, int epilogue);
 ffmi_status ffmi_linear_w4(const void *X, const void *W4_packed, const void *scales, void *Y,
                            int T, int out_dim, int in_dim, int epilogue, void *workspace,
                            size_t workspace_bytes, ffmi_stream stream);
+/* Test hook (host only, no launch): what ffmi_linear_w4 does with these
+ * arguments and workspace_bytes of workspace, in ffmi_debug_linear_w8_plan's
+ * six fields.  NULL plan, T <= 0: FFMI_ERR_INVALID; in_dim % 128:
+ * FFMI_ERR_UNSUPPORTED. */
+ffmi_status ffmi_debug_linear_w4_plan(int T, int out_dim, int in_dim, int epilogue,
+                                      size_t workspace_bytes, int *plan /* [6] */);
 /* Test hook: row-major [out_dim][in_dim] nibble values, one per byte, and
  * [out_dim][in_dim / 32] scale bytes of a packed pair; gate_up 0: plain
  * buffers, 1 / 2: the gate / up matrix of _gate_up buffers. */
@@ -1240,7 +1251,8 @@ const char *ffmi_last_error(void);
  * ffmi_rmsnorm_fp8, ffmi_linear_w8a8(_workspace_bytes), FFMI_MODEL_A8; and
  * MXFP4 weight-only linear layers: ffmi_linear_w4(_packed_bytes, _scale_bytes,
  * _quantize_pack(_gate_up), _workspace_bytes), ffmi_debug_linear_w4_unpack,
- * FFMI_MODEL_W4 */
+ * FFMI_MODEL_W4; and its M-split kernel for 65 .. 256 rows:
+ * ffmi_linear_w4_onepass_workspace_bytes, ffmi_debug_linear_w4_plan */
 const char *ffmi_version(void);
 
 #ifdef __cplusplus

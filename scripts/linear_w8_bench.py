@@ -43,11 +43,19 @@ ffmi_rmsnorm, H = 4096), and the serving part with weight_dtype "fp8" against
 
 --w4: OCP MXFP4 weights (ffmi_linear_w4).  The same five shapes, cold-weight
 protocol and method at T = 8, 32 and 168, three legs alternating in one
-process: "mxfp4" (one pass per 64 rows: three at T = 168; each weight copy has
-its own scale bytes), "fp8" (ffmi_linear_w8 with its one-pass workspace) and
+process: "mxfp4" (with its one-pass workspace: the M-split kernel at T = 168;
+profiles/linear_w4_bench.json predates that kernel and holds three passes of 64
+rows there; each weight copy has its own scale bytes), "fp8" (ffmi_linear_w8 with its one-pass workspace) and
 "fp16".  Then the serving part with weight_dtype "fp16", "fp8" and "mxfp4".
 
     python scripts/linear_w8_bench.py --w4 [--out profiles/linear_w4_bench.json]
+
+--w4 --mid: the M-split MXFP4 kernel, as --mid: T = 72, 128, 168, 256, two worker
+processes, four legs: "onepass" (ffmi_linear_w4 with
+ffmi_linear_w4_onepass_workspace_bytes), "multipass" (the same call under
+FFMI_W4_MULTIPASS=1), "fp8" (ffmi_linear_w8, one-pass) and "fp16".
+
+    python scripts/linear_w8_bench.py --w4 --mid [--out profiles/linear_w4_mid_bench.json]
 """
 import argparse
 import ctypes
@@ -251,7 +259,7 @@ def w4_rows(args):
             Y = Buf.empty((T, N), np.float16)
             nws = max(L.ffmi_linear_workspace_bytes(T, N, K, epi), 16,
                       L.ffmi_linear_w8_onepass_workspace_bytes(T, N, K, epi),
-                      L.ffmi_linear_w4_workspace_bytes(T, N, K, epi))
+                      L.ffmi_linear_w4_onepass_workspace_bytes(T, N, K, epi))
             ws, it = Buf.empty((nws,), np.uint8), [0]
 
             def wt(base, n, b):
@@ -284,7 +292,7 @@ def w4_rows(args):
     return rows
 
 
-def mid_worker():
+def mid_worker(w4):
     """stdin: one JSON command per line -- {"shape": i} (weight copies of SHAPES[i]),
     {"T": t} (activations, output, workspace), {"leg": l, "n": n} (n calls); stdout:
     one JSON reply per command, a timed block's milliseconds for the last."""
@@ -293,7 +301,9 @@ def mid_worker():
     block16 = f16(rng.standard_normal(8 << 20) * 0.02)
     block8 = rng.integers(0, 127, size=16 << 20).astype(np.uint8) | \
         (rng.integers(0, 2, size=16 << 20).astype(np.uint8) << 7)  # (no NaN byte)
-    fp16 = os.environ.get("FFMI_W8_MULTIPASS", "0") == "0"  # (the other worker has no fp16 leg)
+    block4 = rng.integers(0, 256, size=16 << 20).astype(np.uint8)  # (every nibble is a value)
+    # (the multi-pass worker runs its one leg only: no fp16 copies, and under --w4 no fp8 ones)
+    first = os.environ.get("FFMI_W4_MULTIPASS" if w4 else "FFMI_W8_MULTIPASS", "0") == "0"
     st, it = {}, 0
     for line in sys.stdin:
         cmd, out = json.loads(line), {}
@@ -302,10 +312,16 @@ def mid_worker():
             name, N, K, epi = SHAPES[cmd["shape"]]
             g = 2 if epi == F.EPI_SILU_MUL else 1
             b16, b8 = g * L.ffmi_linear_packed_bytes(N, K), g * L.ffmi_linear_w8_packed_bytes(N, K)
-            st.update(N=N, K=K, epi=epi, b16=b16, b8=b8, w8=copies(b8, block8),
-                      w16=copies(b16, block16) if fp16 else None,
+            st.update(N=N, K=K, epi=epi, b16=b16, b8=b8,
+                      w8=copies(b8, block8) if first or not w4 else None,
+                      w16=copies(b16, block16) if first else None,
                       sc=Buf(np.full(g * L.ffmi_linear_w8_scale_count(N), 2.0**-6, np.float32)))
             out = dict(weight_bytes=dict(fp8=int(b8), fp16=int(b16)))
+            if w4:
+                b4, bs4 = g * L.ffmi_linear_w4_packed_bytes(N, K), g * L.ffmi_linear_w4_scale_bytes(N, K)
+                st.update(b4=b4, bs4=bs4, w4=copies(b4, block4))
+                st["sc4"] = Buf(np.full(st["w4"][1] * bs4, 127 - 6, np.uint8))  # (scale bytes per copy)
+                out["weight_bytes"]["mxfp4"] = int(b4 + bs4)
         elif "T" in cmd:
             T, N, K, epi = cmd["T"], st["N"], st["K"], st["epi"]
             X = Buf(f16(rng.standard_normal((T, K))))
@@ -314,7 +330,11 @@ def mid_worker():
             nws = max(L.ffmi_linear_workspace_bytes(T, N, K, epi),
                       L.ffmi_linear_w8_onepass_workspace_bytes(T, N, K, epi), 16)
             plan = (ctypes.c_int * 6)()
-            F.check(L.ffmi_debug_linear_w8_plan(T, N, K, epi, nws, plan))
+            if w4:
+                nws = max(nws, L.ffmi_linear_w4_onepass_workspace_bytes(T, N, K, epi))
+                F.check(L.ffmi_debug_linear_w4_plan(T, N, K, epi, nws, plan))
+            else:
+                F.check(L.ffmi_debug_linear_w8_plan(T, N, K, epi, nws, plan))
             st.update(T=T, X=X, Xp=Xp, Y=Buf.empty((T, N), np.float16), nws=nws,
                       ws=Buf.empty((nws,), np.uint8))
             out = dict(plan=list(plan))
@@ -328,6 +348,11 @@ def mid_worker():
                     F.check(L.ffmi_linear_ws(st["Xp"].ptr, ctypes.c_void_p(w.ptr.value + (it % n) * b),
                                              st["Y"].ptr, T, N, K, epi | F.X_PACKED | F.W_STREAM,
                                              ws.ptr, nws, None))
+                elif w4 and cmd["leg"] != "fp8":
+                    (w, n), b, bs = st["w4"], st["b4"], st["bs4"]
+                    F.check(L.ffmi_linear_w4(st["X"].ptr, ctypes.c_void_p(w.ptr.value + (it % n) * b),
+                                             ctypes.c_void_p(st["sc4"].ptr.value + (it % n) * bs),
+                                             st["Y"].ptr, T, N, K, epi | F.W_STREAM, ws.ptr, nws, None))
                 else:
                     (w, n), b = st["w8"], st["b8"]
                     F.check(L.ffmi_linear_w8(st["X"].ptr, ctypes.c_void_p(w.ptr.value + (it % n) * b),
@@ -339,8 +364,10 @@ def mid_worker():
 
 def mid_rows(args):
     def worker(multipass):
-        env = dict(os.environ, FFMI_W8_MULTIPASS="1" if multipass else "0")
-        return subprocess.Popen([sys.executable, os.path.abspath(__file__), "--mid-worker"], env=env,
+        env = dict(os.environ)
+        env["FFMI_W4_MULTIPASS" if args.w4 else "FFMI_W8_MULTIPASS"] = "1" if multipass else "0"
+        return subprocess.Popen([sys.executable, os.path.abspath(__file__), "--mid-worker"] +
+                                ["--w4"] * args.w4, env=env,
                                 stdin=subprocess.PIPE, stdout=subprocess.PIPE, text=True)
 
     def ask(w, **cmd):
@@ -351,7 +378,7 @@ def mid_rows(args):
             raise RuntimeError(f"worker exited with {w.wait()}")
         return json.loads(line)
     one, multi = worker(False), worker(True)
-    legs = {"onepass": one, "multipass": multi, "fp16": one}
+    legs = {"onepass": one, "multipass": multi, **({"fp8": one} if args.w4 else {}), "fp16": one}
     rows = []
     try:
         for i, (name, N, K, _) in enumerate(SHAPES):
@@ -375,6 +402,8 @@ def mid_rows(args):
                                     spread=round(float((a.max() - a.min()) / np.median(a)), 3))
                 row["multipass_over_onepass"] = round(row["multipass"]["us"] / row["onepass"]["us"], 3)
                 row["fp16_over_onepass"] = round(row["fp16"]["us"] / row["onepass"]["us"], 3)
+                if args.w4:
+                    row["fp8_over_onepass"] = round(row["fp8"]["us"] / row["onepass"]["us"], 3)
                 print(json.dumps(row), flush=True)
                 rows.append(row)
     finally:
@@ -435,8 +464,16 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "linear_w8_bench.json"))
     args = ap.parse_args()
     if args.mid_worker:
-        return mid_worker()
+        return mid_worker(args.w4)
     args.T = args.T or ("8,168" if args.a8 else "72,128,168,256" if args.mid else "8,32,168")
+    if args.w4 and args.mid:
+        res = dict(bench="linear_w4_mid_bench", gemms=mid_rows(args))
+        out = args.out.replace("linear_w8_bench.json", "linear_w4_mid_bench.json")
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        with open(out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+        return
     if args.a8:
         fa.set_device(0)
         gemms, norms = a8_rows(args)
