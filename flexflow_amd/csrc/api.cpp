@@ -931,6 +931,37 @@ extern "C" ffmi_status ffmi_linear_w8a8(const void *X8, const float *row_scales,
   return FFMI_OK;
 }
 
+// W4A8: MXFP4 weights against the same fp8 rows (kernels/gemm_w4a8.hip)
+#define FFMI_W4A8_CHECK(cond, code, why) \
+  do { if (!(cond)) return w8_refuse((code), "w4a8: " why, __LINE__); } while (0)
+
+extern "C" size_t ffmi_linear_w4a8_workspace_bytes(int T, int out_dim, int in_dim, int epilogue) {
+  return ffmi::gemm_w4a8_workspace_bytes(T, out_dim, in_dim, epilogue);
+}
+
+extern "C" ffmi_status ffmi_linear_w4a8(const void *X8, const float *row_scales,
+                                        const void *W4_packed, const void *scales, void *Y, int T,
+                                        int out_dim, int in_dim, int epilogue, void *workspace,
+                                        size_t workspace_bytes, ffmi_stream stream) {
+  FFMI_W4A8_CHECK(X8 && row_scales && W4_packed && scales && Y, FFMI_ERR_INVALID, "null pointer");
+  FFMI_W4A8_CHECK(T >= 0 && out_dim > 0 && in_dim > 0, FFMI_ERR_INVALID,
+                  "T < 0 or an empty matrix");
+  FFMI_W4A8_CHECK(in_dim % 128 == 0, FFMI_ERR_UNSUPPORTED, "in_dim % 128 != 0");
+  FFMI_W4A8_CHECK(!(epilogue & (FFMI_X_PACKED | FFMI_Y_PACKED)), FFMI_ERR_UNSUPPORTED,
+                  "row-major activations only (FFMI_X_PACKED / FFMI_Y_PACKED)");
+  const int base = epilogue & ~FFMI_W_STREAM;
+  FFMI_W4A8_CHECK(base == FFMI_EPI_NONE || base == FFMI_EPI_SILU_MUL, FFMI_ERR_INVALID,
+                  "unknown epilogue");
+  const size_t need = ffmi::gemm_w4a8_workspace_bytes(T, out_dim, in_dim, epilogue);
+  FFMI_W4A8_CHECK(workspace_bytes >= need && (workspace || !need), FFMI_ERR_INVALID,
+                  "workspace smaller than ffmi_linear_w4a8_workspace_bytes");
+  FFMI_HIP(ffmi::launch_gemm_w4a8((const uint8_t *)X8, row_scales, (const uint8_t *)W4_packed,
+                                  (const uint8_t *)scales, (uint16_t *)Y, (float *)workspace,
+                                  workspace_bytes, T, out_dim, in_dim, epilogue,
+                                  (hipStream_t)stream));
+  return FFMI_OK;
+}
+
 extern "C" ffmi_status ffmi_rmsnorm(const void *x, const void *w, void *out, int T, int H,
                                     float eps, ffmi_stream stream) {
   FFMI_CHECK(x && w && out && H % 8 == 0 && H <= 16384, FFMI_ERR_INVALID);

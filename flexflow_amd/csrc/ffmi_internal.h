@@ -431,6 +431,16 @@ hipError_t launch_gemm_w4(const uint16_t *X, const uint8_t *W4, const uint8_t *s
                           float *ws, size_t ws_bytes, int T, int N, int K, int epilogue,
                           hipStream_t s);
 
+// kernels/gemm_w4a8.hip: W4A8 -- the MXFP4 weights above against the e4m3 rows
+// and row scales of launch_quantize_rows_fp8 (or the quantising norm), on the
+// block-scaled MFMA.  No multi-pass route: the workspace is the requirement.
+size_t gemm_w4a8_workspace_bytes(int T, int N, int K, int epilogue);  // slabs for min(T, 256) rows
+// Y [T][N] fp16 rows = a[t] * (x8 . deq^T); epilogues as launch_gemm_w4's; any
+// T: one weight pass per 256 rows (a pass of <= 16 rows in the tile-split form)
+hipError_t launch_gemm_w4a8(const uint8_t *X8, const float *row_scales, const uint8_t *W4,
+                            const uint8_t *scales, uint16_t *Y, float *ws, size_t ws_bytes, int T,
+                            int N, int K, int epilogue, hipStream_t s);
+
 uint64_t weight_key(const char *name, uint64_t seed);
 
 }  // namespace ffmi

@@ -26,9 +26,9 @@ extern "C" ffmi_status ffmi_model_create_ex(const ffmi_llama_config *cfg, const 
              FFMI_ERR_INVALID);
   if (flags & FFMI_MODEL_W4) {
     // one weight format per model; otherwise what the w8 route leaves unbuilt
-    const char *why = (flags & (FFMI_MODEL_W8 | FFMI_MODEL_A8))
-                          ? "w4: not together with FFMI_MODEL_W8 / FFMI_MODEL_A8"
-                      : o->full_precision           ? "w4: fp16 models only (full_precision)"
+    // (with FFMI_MODEL_A8: the W4A8 step)
+    const char *why = (flags & FFMI_MODEL_W8)     ? "w4: not together with FFMI_MODEL_W8"
+                      : o->full_precision          ? "w4: fp16 models only (full_precision)"
                       : o->tp_size > 1              ? "w4: tp_size > 1"
                       : (flags & FFMI_MODEL_LORA)   ? "w4: LoRA adapters on MXFP4 weights are not served"
                                                     : nullptr;
@@ -37,8 +37,9 @@ extern "C" ffmi_status ffmi_model_create_ex(const ffmi_llama_config *cfg, const 
       return FFMI_ERR_UNSUPPORTED;
     }
   }
-  if ((flags & FFMI_MODEL_A8) && !(flags & FFMI_MODEL_W8)) {
-    ffmi_set_last_error("a8: fp8 activations need fp8 weights (FFMI_MODEL_W8)", __FILE__, __LINE__);
+  if ((flags & FFMI_MODEL_A8) && !(flags & (FFMI_MODEL_W8 | FFMI_MODEL_W4))) {
+    ffmi_set_last_error("a8: fp8 activations need fp8 or MXFP4 weights (FFMI_MODEL_W8 / _W4)",
+                        __FILE__, __LINE__);
     return FFMI_ERR_UNSUPPORTED;
   }
   if (flags & FFMI_MODEL_W8) {

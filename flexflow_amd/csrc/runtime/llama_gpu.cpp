@@ -85,14 +85,15 @@ struct LlamaGPU : public ffmi_model {
   // take: no fused residual norms, no deferred slabs, no folded o projection,
   // row-major activations (packed = false)
   bool w8 = false;
-  // FFMI_MODEL_A8 (with w8): every GEMM input is e4m3 rows with one scale per
-  // token (kernels/gemm_w8a8.hip).  x8 / x8_s hold the input of the GEMM about
+  // FFMI_MODEL_A8 (with w8 or w4): every GEMM input is e4m3 rows with one scale
+  // per token (kernels/gemm_w8a8.hip; under w4 kernels/gemm_w4a8.hip).  x8 / x8_s hold the input of the GEMM about
   // to run: written by the quantising norm (qkv, gate/up, lm_head) or by a
   // quantise launch on att / mlp (o, down), consumed before the next is made
   bool a8 = false;
   // FFMI_MODEL_W4: the w8 route (wq = w8 || w4 selects it) with OCP MXFP4
   // weights (kernels/gemm_w4.hip): the byte pointers hold the nibbles, the
   // scale pointers the e8m0 scale bytes, and every GEMM is launch_gemm_w4
+  // (with a8: launch_gemm_w4a8 on the same resident weights)
   bool w4 = false, wq = false;
   uint8_t *x8 = nullptr;
   float *x8_s = nullptr;
@@ -991,6 +992,11 @@ struct LlamaGPU : public ffmi_model {
                              ffmi::gemm_w4_onepass_workspace_bytes(Tm, H, Hl, 0),
                              ffmi::gemm_w4_onepass_workspace_bytes(Tm, H, Fl, 0),
                              ffmi::gemm_w4_onepass_workspace_bytes(Tm, Vl, H, 0)});
+      if (w4 && a8)  // (kernels/gemm_w4a8.hip: the one-pass size is the requirement)
+        ws_bytes = std::max({ffmi::gemm_w4a8_workspace_bytes(Tm, Nqkv, H, 0),
+                             ffmi::gemm_w4a8_workspace_bytes(Tm, H, Hl, 0),
+                             ffmi::gemm_w4a8_workspace_bytes(Tm, H, Fl, 0),
+                             ffmi::gemm_w4a8_workspace_bytes(Tm, Vl, H, 0)});
       for (int t = 16; t <= Tm && !wq; t += 16) {
         const size_t w1 = ffmi_linear_workspace_bytes(t, Nqkv, H, FFMI_EPI_NONE);
         const size_t w2 = ffmi_linear_workspace_bytes(t, H, Hl, FFMI_EPI_NONE);
@@ -1537,8 +1543,12 @@ struct LlamaGPU : public ffmi_model {
                      int epi) -> ffmi_status {
       if (a8) {
         if (X != h || !norm8) FFMI_HIP(ffmi::launch_quantize_rows_fp8(X, T, K, x8, x8_s, stream));
-        FFMI_HIP(ffmi::launch_gemm_w8a8(x8, x8_s, W, sc, Y, ws, ws_bytes, T, N, K, epi | wstream,
-                                        stream));
+        if (w4)
+          FFMI_HIP(ffmi::launch_gemm_w4a8(x8, x8_s, W, reinterpret_cast<const uint8_t *>(sc), Y, ws,
+                                          ws_bytes, T, N, K, epi | wstream, stream));
+        else
+          FFMI_HIP(ffmi::launch_gemm_w8a8(x8, x8_s, W, sc, Y, ws, ws_bytes, T, N, K, epi | wstream,
+                                          stream));
         return FFMI_OK;
       }
       if (w4) {
@@ -1986,8 +1996,8 @@ ffmi_status create_llama_gpu(const ffmi_llama_config *cfg, const ffmi_model_opts
   m->lora = (flags & FFMI_MODEL_LORA) != 0;
   m->kv_fp8 = (flags & FFMI_MODEL_KV_FP8) != 0;
   m->w8 = (flags & FFMI_MODEL_W8) != 0;
-  m->a8 = m->w8 && (flags & FFMI_MODEL_A8) != 0;
   m->w4 = (flags & FFMI_MODEL_W4) != 0;
+  m->a8 = (m->w8 || m->w4) && (flags & FFMI_MODEL_A8) != 0;
   m->wq = m->w8 || m->w4;
   if (m->lora && (o->mode == FFMI_MODEL_BEAM || o->tp_size > 1)) {
     delete m;

@@ -40,7 +40,7 @@ MODEL_NATIVE_GQA = 1
 MODEL_LORA = 4  # (2 is left unassigned: it stays an invalid flag)
 MODEL_KV_FP8 = 16  # (8, like 2, is left unassigned: it stays an invalid flag)
 MODEL_W8 = 32  # fp8 (e4m3) weight-only linear layers
-MODEL_A8 = 128  # with MODEL_W8: fp8 activations, one dynamic scale per token
+MODEL_A8 = 128  # with MODEL_W8 or MODEL_W4: fp8 activations, one dynamic scale per token
 MODEL_W4 = 256  # OCP MXFP4 weight-only linear layers
 ATTN_KV_FP8 = 1  # ffmi_attn_create_ex flag: an 8-bit (e4m3) KV cache
 LORA_MAX_ADAPTERS, LORA_MAX_RANK = 8, 64
@@ -211,6 +211,9 @@ SIGNATURES = {
                                  c_int, c_float, c_void_p]),
     "ffmi_linear_w8a8_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "ffmi_linear_w8a8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                 c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "ffmi_linear_w4a8_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "ffmi_linear_w4a8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                  c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "ffmi_model_weight_bytes": (c_size_t, [c_void_p]),
     "ffmi_rmsnorm": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),

@@ -63,16 +63,18 @@ class Model:
         (FFMI_MODEL_W4: about 0.27 of the fp16 weight bytes; as "fp8", and
         hidden, heads * head_dim and intermediate multiples of 128); "fp16" is
         the default model.
-        activation_dtype "fp8" (with weight_dtype "fp8" only): every linear
-        layer's input is e4m3 with one dynamic scale per token and runs on the
-        fp8 matrix instruction (FFMI_MODEL_A8); the residual stream, attention
-        and logits stay fp16."""
+        activation_dtype "fp8" (with weight_dtype "fp8" or "mxfp4"): every
+        linear layer's input is e4m3 with one dynamic scale per token
+        (FFMI_MODEL_A8) and runs on the fp8 matrix instruction (W8A8) or, with
+        "mxfp4" weights, on the block-scaled fp4 x fp8 one (W4A8, the same
+        resident weights as W4A16); the residual stream, attention and logits
+        stay fp16."""
         if weight_dtype not in ("fp16", "fp8", "mxfp4"):
             raise ValueError(f"weight_dtype {weight_dtype!r}: 'fp16', 'fp8' or 'mxfp4'")
         if activation_dtype not in ("fp16", "fp8"):
             raise ValueError(f"activation_dtype {activation_dtype!r}: 'fp16' or 'fp8'")
-        if activation_dtype == "fp8" and weight_dtype != "fp8":
-            raise ValueError("activation_dtype='fp8' needs weight_dtype='fp8'")
+        if activation_dtype == "fp8" and weight_dtype == "fp16":
+            raise ValueError("activation_dtype='fp8' needs weight_dtype='fp8' or 'mxfp4'")
         if kv_cache_dtype not in ("fp16", "fp8"):
             raise ValueError(f"kv_cache_dtype {kv_cache_dtype!r}: 'fp16' or 'fp8'")
         fp8 = kv_cache_dtype == "fp8"

@@ -389,6 +389,27 @@ ffmi_status ffmi_linear_w8a8(const void *X8, const float *row_scales, const void
                              int epilogue, void *workspace, size_t workspace_bytes,
                              ffmi_stream stream);
 
+/* W4A8 (kernels/gemm_w4a8.hip): the packed MXFP4 weights of
+ * ffmi_linear_w4_quantize_pack(_gate_up), as they are, against the X8 /
+ * row_scales of ffmi_quantize_rows_fp8 / ffmi_rmsnorm_fp8, as they are, on the
+ * block-scaled matrix instruction (fp4 x fp8, one e8m0 scale per 32 k applied
+ * in hardware, fp32 accumulation):
+ *   Y[t][n] = a[t] * sum_k x8[t][k] * e2m1(nibble[n][k]) * 2^e(n, k / 32).
+ * in_dim % 128 == 0.  epilogue FFMI_EPI_NONE or FFMI_EPI_SILU_MUL, optionally |
+ * FFMI_W_STREAM.  One kernel family covers 1 .. 256 rows per weight pass (up
+ * to 16 rows the four waves split the weight tiles, above they split the
+ * rows); more rows run one pass per 256.  A row's result depends on the row,
+ * out_dim, in_dim and the epilogue only.  workspace: at least
+ * ffmi_linear_w4a8_workspace_bytes (slabs for min(T, 256) rows; 0 for shapes
+ * that do not split K) -- there is no multi-pass route with less.
+ * Refusals as ffmi_linear_w8a8's (in_dim % 128), naming "w4a8" in
+ * ffmi_last_error. */
+size_t ffmi_linear_w4a8_workspace_bytes(int T, int out_dim, int in_dim, int epilogue);
+ffmi_status ffmi_linear_w4a8(const void *X8, const float *row_scales, const void *W4_packed,
+                             const void *scales, void *Y, int T, int out_dim, int in_dim,
+                             int epilogue, void *workspace, size_t workspace_bytes,
+                             ffmi_stream stream);
+
 /* ------------------------------------------------------------------------ */
 /* Norms (replace Kernels::RMSNorm / ResidualRMSNorm inference_kernel_wrapper, */
 /* rms_norm_kernels.h:50-54, residual_rms_norm_kernels.h:53-59)              */
@@ -760,8 +781,10 @@ ffmi_status ffmi_model_set_kv_scales(ffmi_model *m, float k_scale, float v_scale
  *   norm (ffmi_rmsnorm_fp8) and a ffmi_quantize_rows_fp8 launch before o_proj
  *   and before down_proj; the residual stream, the attention and the logits
  *   stay fp16; weights and ffmi_model_weight_bytes are those of W8.  Valid
- *   only together with FFMI_MODEL_W8 (alone: FFMI_ERR_UNSUPPORTED, "a8" in
- *   ffmi_last_error); W8's refusals carry over.
+ *   only together with FFMI_MODEL_W8 or FFMI_MODEL_W4 (alone:
+ *   FFMI_ERR_UNSUPPORTED, "a8" in ffmi_last_error); W8's refusals carry over.
+ *   With FFMI_MODEL_W4 it is the same step on the W4 model's resident nibbles
+ *   and scale bytes with every GEMM ffmi_linear_w4a8; W4's refusals carry over.
  *   (bit value 128: 64, like 2 and 8, stays an unknown flag, FFMI_ERR_INVALID) */
 #define FFMI_MODEL_A8 128u
 /*   FFMI_MODEL_W4: the linear layers keep OCP MXFP4 nibbles with one e8m0
@@ -771,7 +794,7 @@ ffmi_status ffmi_model_set_kv_scales(ffmi_model *m, float k_scale, float v_scale
  *   step is FFMI_MODEL_W8's with every GEMM ffmi_linear_w4.  All three modes,
  *   with FFMI_MODEL_NATIVE_GQA and FFMI_MODEL_KV_FP8, eager and under graph
  *   replay.  FFMI_ERR_UNSUPPORTED ("w4" in ffmi_last_error): together with
- *   FFMI_MODEL_W8 or FFMI_MODEL_A8, full_precision, tp_size > 1,
+ *   FFMI_MODEL_W8 (with or without FFMI_MODEL_A8), full_precision, tp_size > 1,
  *   FFMI_MODEL_LORA, hidden, heads * head_dim or intermediate not a multiple
  *   of 128.
  *   (bit value 256; 2, 8 and 64 stay unknown flags) */
@@ -1252,7 +1275,9 @@ const char *ffmi_last_error(void);
  * MXFP4 weight-only linear layers: ffmi_linear_w4(_packed_bytes, _scale_bytes,
  * _quantize_pack(_gate_up), _workspace_bytes), ffmi_debug_linear_w4_unpack,
  * FFMI_MODEL_W4; and its M-split kernel for 65 .. 256 rows:
- * ffmi_linear_w4_onepass_workspace_bytes, ffmi_debug_linear_w4_plan */
+ * ffmi_linear_w4_onepass_workspace_bytes, ffmi_debug_linear_w4_plan; and
+ * MXFP4 weights against fp8 activations (W4A8): ffmi_linear_w4a8
+ * (_workspace_bytes), FFMI_MODEL_W4 | FFMI_MODEL_A8 */
 const char *ffmi_version(void);
 
 #ifdef __cplusplus

@@ -56,6 +56,17 @@ ffmi_linear_w4_onepass_workspace_bytes), "multipass" (the same call under
 FFMI_W4_MULTIPASS=1), "fp8" (ffmi_linear_w8, one-pass) and "fp16".
 
     python scripts/linear_w8_bench.py --w4 --mid [--out profiles/linear_w4_mid_bench.json]
+
+--w4 --a8: W4A8 (MXFP4 weights against fp8 rows on the block-scaled matrix
+instruction).  The five shapes, cold-weight protocol and method at T = 8, 32,
+168 and 256, four legs alternating in one process: "w4a8" (ffmi_linear_w4a8; for
+o_proj and down the ffmi_quantize_rows_fp8 launch ahead of it is inside the
+timed call), "w4a16" (ffmi_linear_w4 with its one-pass workspace: the skinny
+kernel up to 64 rows, the M-split one above), "w8a8" (ffmi_linear_w8a8, with
+the same quantise launch) and "fp16".  Then the serving part with weight_dtype
+"mxfp4" against "mxfp4" + activation_dtype "fp8".
+
+    python scripts/linear_w8_bench.py --w4 --a8 [--out profiles/linear_w4a8_bench.json]
 """
 import argparse
 import ctypes
@@ -292,6 +303,70 @@ def w4_rows(args):
     return rows
 
 
+def w4a8_rows(args):
+    L, rng, rows = F.lib(), np.random.default_rng(0), []
+    block16 = f16(rng.standard_normal(8 << 20) * 0.02)
+    block8 = rng.integers(0, 127, size=16 << 20).astype(np.uint8) | \
+        (rng.integers(0, 2, size=16 << 20).astype(np.uint8) << 7)  # (no NaN byte)
+    block4 = rng.integers(0, 256, size=16 << 20).astype(np.uint8)  # (every nibble is a value)
+    for name, N, K, epi in SHAPES:
+        g = 2 if epi == F.EPI_SILU_MUL else 1
+        b16, b8 = g * L.ffmi_linear_packed_bytes(N, K), g * L.ffmi_linear_w8_packed_bytes(N, K)
+        b4, bs4 = g * L.ffmi_linear_w4_packed_bytes(N, K), g * L.ffmi_linear_w4_scale_bytes(N, K)
+        (w16, n16), (w8, n8), (w4, n4) = copies(b16, block16), copies(b8, block8), copies(b4, block4)
+        sc8 = Buf(np.full(g * L.ffmi_linear_w8_scale_count(N), 2.0**-6, np.float32))
+        sc4 = Buf(np.full(n4 * bs4, 127 - 6, np.uint8))  # (a copy of the scale bytes per weight copy)
+        quant = name in ("o_proj", "down")  # (the other inputs come quantised from a norm)
+        for T in [int(t) for t in args.T.split(",")]:
+            X = Buf(f16(rng.standard_normal((T, K))))
+            Xp = Buf.empty((L.ffmi_packed_activation_bytes(T, K),), np.uint8)
+            F.check(L.ffmi_pack_activations(X.ptr, T, K, Xp.ptr, None))
+            X8, xs, Y = Buf.empty((T, K), np.uint8), Buf.empty((T,), np.float32), Buf.empty((T, N), np.float16)
+            F.check(L.ffmi_quantize_rows_fp8(X.ptr, T, K, X8.ptr, xs.ptr, None))
+            nws = max(L.ffmi_linear_workspace_bytes(T, N, K, epi), 16,
+                      L.ffmi_linear_w8a8_workspace_bytes(T, N, K, epi),
+                      L.ffmi_linear_w4_onepass_workspace_bytes(T, N, K, epi),
+                      L.ffmi_linear_w4a8_workspace_bytes(T, N, K, epi))
+            ws, it = Buf.empty((nws,), np.uint8), [0]
+
+            def wt(base, n, b):
+                return ctypes.c_void_p(base.ptr.value + (it[0] % n) * b)
+
+            def a8(n, w4_leg):
+                for _ in range(n):
+                    it[0] += 1
+                    if quant:
+                        F.check(L.ffmi_quantize_rows_fp8(X.ptr, T, K, X8.ptr, xs.ptr, None))
+                    if w4_leg:
+                        F.check(L.ffmi_linear_w4a8(X8.ptr, xs.ptr, wt(w4, n4, b4), wt(sc4, n4, bs4), Y.ptr,
+                                                   T, N, K, epi | F.W_STREAM, ws.ptr, nws, None))
+                    else:
+                        F.check(L.ffmi_linear_w8a8(X8.ptr, xs.ptr, wt(w8, n8, b8), sc8.ptr, Y.ptr, T, N, K,
+                                                   epi | F.W_STREAM, ws.ptr, nws, None))
+
+            def w4a16(n):
+                for _ in range(n):
+                    it[0] += 1
+                    F.check(L.ffmi_linear_w4(X.ptr, wt(w4, n4, b4), wt(sc4, n4, bs4), Y.ptr, T, N, K,
+                                             epi | F.W_STREAM, ws.ptr, nws, None))
+
+            def fp16(n):
+                for _ in range(n):
+                    it[0] += 1
+                    F.check(L.ffmi_linear_ws(Xp.ptr, wt(w16, n16, b16), Y.ptr, T, N, K,
+                                             epi | F.X_PACKED | F.W_STREAM, ws.ptr, nws, None))
+            res, block = timed_legs(args, dict(w4a8=lambda n: a8(n, True), w4a16=w4a16,
+                                               w8a8=lambda n: a8(n, False), fp16=fp16))
+            row = dict(gemm=name, T=T, N=N, K=K, rounds=args.rounds, calls_per_block=block,
+                       a8_includes_quantise=quant,
+                       weight_bytes=dict(mxfp4=int(b4 + bs4), fp8=int(b8), fp16=int(b16)), **res)
+            for leg in ("w4a16", "w8a8", "fp16"):
+                row[leg + "_over_w4a8"] = round(res[leg]["us"] / res["w4a8"]["us"], 3)
+            print(json.dumps(row), flush=True)
+            rows.append(row)
+    return rows
+
+
 def mid_worker(w4):
     """stdin: one JSON command per line -- {"shape": i} (weight copies of SHAPES[i]),
     {"T": t} (activations, output, workspace), {"leg": l, "n": n} (n calls); stdout:
@@ -420,7 +495,9 @@ def serve(args):
         cfg["num_layers"] = args.layers
     rm_kw = dict(max_requests_per_batch=B, max_tokens_per_batch=1024, max_sequence_length=512)
     prompts = make_prompts(B, P - 1, cfg["vocab_size"])
-    kinds = {"fp8": dict(weight_dtype="fp8"), "fp8_a8": dict(weight_dtype="fp8", activation_dtype="fp8")} \
+    kinds = {"mxfp4": dict(weight_dtype="mxfp4"),
+             "mxfp4_a8": dict(weight_dtype="mxfp4", activation_dtype="fp8")} if args.a8 and args.w4 else \
+        {"fp8": dict(weight_dtype="fp8"), "fp8_a8": dict(weight_dtype="fp8", activation_dtype="fp8")} \
         if args.a8 else {d: dict(weight_dtype=d) for d in ("fp16", "fp8") + (("mxfp4",) if args.w4 else ())}
     models = {d: fa.Model(cfg, "inc", max_requests=B, max_tokens=1024, max_seq_len=512,
                           weight_seed=20250117, **kw) for d, kw in kinds.items()}
@@ -440,10 +517,11 @@ def serve(args):
     med = {d: sorted(v)[len(v) // 2] for d, v in rates.items()}
     out = dict(workload=f"llama7b_incr B={B} P={P} D={D} layers={cfg['num_layers']}",
                generates_per_window=args.generates, tokens_per_s=rates, median=med,
-               **({"fp8_a8_over_fp8": round(med["fp8_a8"] / med["fp8"], 4)} if args.a8 else
+               **({"mxfp4_a8_over_mxfp4": round(med["mxfp4_a8"] / med["mxfp4"], 4)} if args.a8 and args.w4 else
+                  {"fp8_a8_over_fp8": round(med["fp8_a8"] / med["fp8"], 4)} if args.a8 else
                   {"fp8_over_fp16": round(med["fp8"] / med["fp16"], 4)}),
                **({"mxfp4_over_fp16": round(med["mxfp4"] / med["fp16"], 4),
-                   "mxfp4_over_fp8": round(med["mxfp4"] / med["fp8"], 4)} if args.w4 else {}),
+                   "mxfp4_over_fp8": round(med["mxfp4"] / med["fp8"], 4)} if args.w4 and not args.a8 else {}),
                weight_bytes={d: m.weight_bytes() for d, m in models.items()})
     print(json.dumps(out), flush=True)
     return out
@@ -465,10 +543,21 @@ def main():
     args = ap.parse_args()
     if args.mid_worker:
         return mid_worker(args.w4)
-    args.T = args.T or ("8,168" if args.a8 else "72,128,168,256" if args.mid else "8,32,168")
+    args.T = args.T or ("8,32,168,256" if args.a8 and args.w4 else "8,168" if args.a8 else "72,128,168,256" if args.mid else "8,32,168")
     if args.w4 and args.mid:
         res = dict(bench="linear_w4_mid_bench", gemms=mid_rows(args))
         out = args.out.replace("linear_w8_bench.json", "linear_w4_mid_bench.json")
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        with open(out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+        return
+    if args.a8 and args.w4:
+        fa.set_device(0)
+        res = dict(bench="linear_w4a8_bench", gemms=w4a8_rows(args))
+        if args.serve:
+            res["serving"] = serve(args)
+        out = args.out.replace("linear_w8_bench.json", "linear_w4a8_bench.json")
         os.makedirs(os.path.dirname(out), exist_ok=True)
         with open(out, "w") as f:
             json.dump(res, f, indent=1)
